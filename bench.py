@@ -7,8 +7,12 @@ on the synthetic 'bat' scene of BASELINE.md: a 2048-ray render at a random non-k
 collocation points, backward of all of it and the Adam step.  value = rays rendered per second
 (2 x 2048 per step per GPU), whole job.
 
-  python bench.py [--gpus N --steps K --warmup W --workload cfg3|cfg2 --mode fused|dropin --live --scaling weak|strong]
+  python bench.py [--gpus N --steps K --warmup W --workload cfg3|cfg2 --mode fused|dropin --live --scaling weak|strong] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, ...).  `--full` adds what the headline
+does not need: the profiled pass (`roofline`, `work_per_step`), the CPU baseline (`cpu_baseline`, `reference_cpu`) and the `extras`.
+`--dump-outputs DIR` writes what the timed step returned in its last iteration as DIR/<name>.npy (float32; same arguments, same inputs).
 
 The workload is STATIONARY by default: the optimiser step is executed in full every iteration, but on a shadow copy of the
 parameters (same tensors, same kernels, same bytes), so the field - and with it the number of valid / appearance-masked
@@ -21,7 +25,7 @@ buffer, the regulariser value+gradient kernels, the one-launch Adam, the PDE ter
 `--mode dropin` is the reference's loop body verbatim on the `models` alias: plain autograd, torch.optim.Adam, torch-op
 regularisers, `if loss_vel > 0`, the `.item()` calls - what train_nvfi.py gets without touching it.
 
-The timed region carries no instrumentation.  The roofline figures come from a second, profiled pass over the same number of
+The timed region carries no instrumentation.  The roofline figures (--full) come from a second, profiled pass over the same number of
 steps (HIP events around every launch of a kernel class, on the launch stream).
 """
 import argparse
@@ -218,6 +222,7 @@ class Step:
         self.L1w, self.tvd, self.tva, self.vw = 8e-4, 1.0, 1.0, 1.0
         self.counters = []
         self.pde_counters = []
+        self.last_rgb = {}       # render index -> (R, 3) colours of the last iteration
         self.stepped = False
         self.fused_regs = True
         from nvfi_amd.dist import PdeGradStage
@@ -325,7 +330,7 @@ class Step:
     def _render_term(self, t, k, jit, wait=None):
         """one training render + its mse + the backward of both, gradients accumulated in place (field.render_mse_backward_)"""
         f = self.m.nvfi
-        loss, _ = f.render_mse_backward_(t, self.d_ro[k], self.d_rd[k], self.d_tg[k], white_bg=self.white_bg, jitter=jit, wait_before_backward=wait)
+        loss, self.last_rgb[k] = f.render_mse_backward_(t, self.d_ro[k], self.d_rd[k], self.d_tg[k], white_bg=self.white_bg, jitter=jit, wait_before_backward=wait)
         self.counters.append(f.last_counters)
         return loss
 
@@ -496,7 +501,7 @@ class GraphedStep:
                 s.last_lv = m.get_vel_loss(s.n_pts, points=s.d_pts, t=s.d_t)
             with torch.cuda.stream(s_r1):
                 s_r1.wait_event(start)
-                f.render_mse_backward_(DT(19.0 / 60.0, rec[0:1]), s.d_ro[0], s.d_rd[0], s.d_tg[0], white_bg=True, jitter=jit[0])      # plan: a non-keyframe time (1 RK2 step)
+                _, s.last_rgb[0] = f.render_mse_backward_(DT(19.0 / 60.0, rec[0:1]), s.d_ro[0], s.d_rd[0], s.d_tg[0], white_bg=True, jitter=jit[0])      # plan: a non-keyframe time (1 RK2 step)
                 self.flags.append(f.last_counters)
         early_regs = not cfg3 and os.environ.get("NVFI_EARLY_REGS", "1") != "0"      # single chain: the regulariser pass beside the forward (Step.__call__)
         if early_regs:
@@ -506,8 +511,8 @@ class GraphedStep:
             with torch.cuda.stream(s._s_reg):
                 s.last_regs = f.regularizers_backward_(rec[2:5])
         # plan: a keyframe time / any time without a velocity field
-        loss, _ = f.render_mse_backward_(DT(0.05 if cfg3 else 0.3, rec[1:2]), s.d_ro[-1], s.d_rd[-1], s.d_tg[-1], white_bg=True, jitter=jit[-1],
-                                         wait_before_backward=s._s_reg if early_regs else None)
+        loss, s.last_rgb[len(s.d_ro) - 1] = f.render_mse_backward_(DT(0.05 if cfg3 else 0.3, rec[1:2]), s.d_ro[-1], s.d_rd[-1], s.d_tg[-1], white_bg=True,
+                                                                   jitter=jit[-1], wait_before_backward=s._s_reg if early_regs else None)
         self.flags.append(f.last_counters)
         if cfg3:
             main.wait_stream(s_pde); main.wait_stream(s_r1)
@@ -548,12 +553,12 @@ class GraphedStep:
             start = torch.cuda.Event(); start.record(main)
             with torch.cuda.stream(s_r1):
                 s_r1.wait_event(start)
-                f.render_mse_backward_(DT(19.0 / 60.0, rec[0:1]), s.d_ro[0], s.d_rd[0], s.d_tg[0], white_bg=True, jitter=jit[0])
+                _, s.last_rgb[0] = f.render_mse_backward_(DT(19.0 / 60.0, rec[0:1]), s.d_ro[0], s.d_rd[0], s.d_tg[0], white_bg=True, jitter=jit[0])
                 self.flags.append(f.last_counters)
         else:
-            f.render_mse_backward_(DT(19.0 / 60.0, rec[0:1]), s.d_ro[0], s.d_rd[0], s.d_tg[0], white_bg=True, jitter=jit[0])
+            _, s.last_rgb[0] = f.render_mse_backward_(DT(19.0 / 60.0, rec[0:1]), s.d_ro[0], s.d_rd[0], s.d_tg[0], white_bg=True, jitter=jit[0])
             self.flags.append(f.last_counters)
-        loss, _ = f.render_mse_backward_(DT(0.05, rec[1:2]), s.d_ro[-1], s.d_rd[-1], s.d_tg[-1], white_bg=True, jitter=jit[-1])
+        loss, s.last_rgb[len(s.d_ro) - 1] = f.render_mse_backward_(DT(0.05, rec[1:2]), s.d_ro[-1], s.d_rd[-1], s.d_tg[-1], white_bg=True, jitter=jit[-1])
         self.flags.append(f.last_counters)
         if s_r1 is not main:
             main.wait_stream(s_r1)
@@ -667,9 +672,10 @@ class GraphedStep:
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) / 4 * 1e3
             self.capture_ms.append(ms)
-            if best is None or ms < best[0]:
-                best = (ms, self.graph, self.graphs, s.streams, self._gstream, self.flags)
-        _, self.graph, self.graphs, s.streams, self._gstream, self.flags = best
+            if best is None or ms < best[0]:      # (with the buffers this capture's replays write: loss, colours, PDE loss, regularisers)
+                best = (ms, self.graph, self.graphs, s.streams, self._gstream, self.flags, self.loss, dict(s.last_rgb), getattr(s, "last_lv", None), s.last_regs)
+        _, self.graph, self.graphs, s.streams, self._gstream, self.flags, self.loss, s.last_rgb, s.last_lv, s.last_regs = best
+        self._outs = (dict(s.last_rgb), s.last_lv, s.last_regs)
         self.turn = 0
 
     def __call__(self):
@@ -704,6 +710,9 @@ class GraphedStep:
             self.host_record()
             g.replay()
         self.turn = getattr(self, "turn", 0) + 1
+        outs = getattr(self, "_outs", None)
+        if outs is not None:        # what the replay writes (eager calls of the same Step in between point these at their own tensors)
+            self.s.last_rgb, self.s.last_lv, self.s.last_regs = dict(outs[0]), outs[1], outs[2]
         if depth > 0:
             e = torch.cuda.Event()
             e.record()
@@ -783,6 +792,7 @@ class DropinStep:
                 i = int(self.rng.integers(0, 46))
             rays, target = self.batch()
             rgb_map = self.ren.render(i / 60.0, rays, white_background=True, mode="train")[0]
+            self.last_rgb = {0: rgb_map}
             rgb_loss = torch.nn.functional.mse_loss(rgb_map[..., :3], target[..., :3])
             loss = rgb_loss
             mark()
@@ -792,8 +802,10 @@ class DropinStep:
             t_key = 3 * int(self.rng.integers(0, 16)) / 60.0
         else:
             t_key = float(self.rng.integers(0, 46)) / 60.0
+            self.last_rgb = {}
         rays, target = self.batch()
         rgb_map = self.ren.render(t_key, rays, white_background=True, mode="train")[0]
+        self.last_rgb[len(self.last_rgb)] = rgb_map
         rgb_loss0 = torch.nn.functional.mse_loss(rgb_map[..., :3], target[..., :3])
         loss = loss + 1.0 * rgb_loss0
         self.counters.append(f.last_counters)
@@ -859,7 +871,7 @@ class SegmStep:
         if ev is not None:
             self.advect_events.append(ev)
             self.advect_evals += int(xyz.shape[0]) * int(np.ceil(t / (0.5 * f.tmax / (f.num_keyframes - 1)) - 1e-6))
-        mask = self.mf(xyz)
+        mask = self.last_mask = self.mf(xyz)
         target = (flow / (flow.norm(dim=1, keepdim=True) + 1e-9))[:, :1]
         loss = ((mask[:, :1] - target) ** 2).mean() - 1e-3 * (mask * torch.log(mask + 1e-8)).sum(1).mean()
         self.opt.zero_grad(set_to_none=True)
@@ -888,15 +900,18 @@ def segm_main(args, device):
     torch.cuda.synchronize()
     step.points = step.steps_rk = 0
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(step, last))
     pts, evals = step.points / args.steps, 2.0 * step.steps_rk / args.steps
-    # the dominant kernel - integrate_pos' RK2 advection (k_rk2_x6w since round 6) - bracketed by HIP events on its own stream in a second pass
-    step.time_advect = True
+    # --full: the dominant kernel - integrate_pos' RK2 advection (k_rk2_x6w since round 6) - bracketed by HIP events on its own stream in a second pass
+    step.time_advect = args.full
     step.advect_events, step.advect_evals = [], 0
-    for _ in range(min(args.steps, 5)):
+    for _ in range(min(args.steps, 5) if args.full else 0):
         step()
     torch.cuda.synchronize()
     adv_ms = sum(a.elapsed_time(b) for a, b in step.advect_events)
@@ -926,7 +941,9 @@ def segm_main(args, device):
                         "ms_per_launch": adv_ms / max(1, len(step.advect_events)),
                         "whole_step": {"achieved": flop / (dt / args.steps) / 1e12, "unit": "TFLOP/s (algorithmic fp32 FLOPs of integrate_pos + MaskField GEMMs / step time)"},
                         "gflop_per_step": {"integrate_pos": evals * VEL_FLOP / 1e9, "maskfield": mf_flop / 1e9}}}
-    if not args.no_cpu_baseline:
+    if not args.full:
+        out["roofline"] = None
+    if args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = segm_cpu_baseline(model, step, "chessboard" if scene == "chessboard" else "bat")
         except Exception as e:
@@ -1040,6 +1057,54 @@ def _load_json(name):
         return None
 
 
+PILOT_ROUNDS, PILOT_STEPS = 2, 10      # --graph auto: untimed steps of each launch mode that pick the one the K timed steps run
+DUMP_SAMPLED_BYTES = 48 << 20      # --dump-outputs: budget of the sampled parameter / moment tensors (the whole dump stays under 64 MB)
+
+
+def _sample(t, n, seed):
+    """float32 numpy copy of the flattened tensor, or of a fixed, seeded sample of n of its elements (sorted indices) when it has more"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), n, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def step_outputs(step, last):
+    """What a caller of the timed step received from its last iteration, as float32 arrays: the loss the step returned, the colours of its
+    renders, the PDE loss and the three regulariser values (fused driver), the MaskField output (segm), and the parameters the optimiser
+    stepped with the first moment of their gradients (a fixed, seeded sample of each large tensor)."""
+    out = {}
+
+    def put(name, v):
+        if torch.is_tensor(v):
+            out[name] = v.detach().float().cpu().numpy()
+        elif isinstance(v, (int, float)):
+            out[name] = np.asarray(v, np.float32)
+
+    put("loss", last)
+    for k, rgb in sorted((getattr(step, "last_rgb", None) or {}).items()):
+        put(f"rgb_render{k}", rgb)
+    put("loss_vel", getattr(step, "last_lv", None))
+    put("regularizers", getattr(step, "last_regs", None))
+    put("mask", getattr(step, "last_mask", None))
+    params = [p for g in step.opt.param_groups for p in g["params"]]
+    tensors = [(f"param_{i:02d}", p, i) for i, p in enumerate(params)]
+    tensors += [(f"adam_exp_avg_{i:02d}", step.opt.state[p]["exp_avg"], i) for i, p in enumerate(params) if "exp_avg" in step.opt.state.get(p, {})]
+    cap = 1 << 22
+    while cap > 1 and 4 * sum(min(t.numel(), cap) for _, t, _ in tensors) > DUMP_SAMPLED_BYTES:
+        cap //= 2
+    for name, t, i in tensors:      # seeded by the parameter's index: param_i and adam_exp_avg_i hold the same elements
+        out[name] = _sample(t, cap, seed=i)
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _spawn_ranks(n, ndev, backend):
     """Re-run this command as n ranks under torch.distributed.run (one process per GPU).  Returns the launcher's exit code."""
     import socket
@@ -1074,13 +1139,17 @@ def main():
     ap.add_argument("--pts", type=int, default=None, help="PDE collocation points per step (default: the scene's vel_reg_n_pts: 262144 bat, 131072 chessboard)")
     ap.add_argument("--grid", type=int, default=199)
     ap.add_argument("--samples", type=int, default=128)
-    ap.add_argument("--profile-steps", type=int, default=-1, help="steps of the separate profiled pass (default: min(steps, 5); 0: none)")
+    ap.add_argument("--profile-steps", type=int, default=-1, help="steps of the separate profiled pass (default: min(steps, 5) with --full, else none; 0: none)")
     ap.add_argument("--prime", type=int, default=8, help="setup iterations before the W warm-up steps (first-touch of the workspaces, allocator pools of the three streams, clocks): the first ~5 iterations of a process run 5-10 %% slower than steady state")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the short extra runs whose results are attached to the default line under `extras` "
                     "(the reference's loop body verbatim, the radiance-only workload, the opt-in prefilter)")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the whole iteration as one captured hipGraph with a device-side time schedule (auto: on for the single-GPU fused driver)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the profiled pass (roofline, work_per_step), the CPU "
+                    "baseline and reference_cpu, and the extras (each still switched off by --profile-steps 0 / --no-cpu-baseline / --no-extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed step returned in its last "
+                    "iteration as DIR/<name>.npy (float32; large tensors as a fixed, seeded sample; under 64 MB in all)")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -1091,28 +1160,18 @@ def main():
         # `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, RCCL rendezvous on 127.0.0.1) - the same
         # command line the driver uses with torch.distributed.run in front
         sys.exit(_spawn_ranks(args.gpus, ndev, backend))
-    graph_line = None
+    auto_pick = False
     if args.workload in ("chessboard", "segm"):
         args.graph = "off"           # (the captured iteration is the bat loop's)
     if (args.graph == "auto" and args.mode == "fused" and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not os.environ.get("NVFI_TORCH_ADAM")
             and not os.environ.get("NVFI_BENCH_CHILD")):
-        # auto: measure BOTH launch modes of the same step and report the faster one (both values go into the line).  The hipGraph replay
-        # takes the host out of the iteration - its time does not depend on the host's launch rate - while eager launches on three streams
-        # are ~3 % faster when the host keeps up (rocprof: the graph's branches start a little later).  The captured-graph run happens in
-        # a child process: a fault inside a graph replay (a runtime bug, see above) kills the process and cannot be caught.
-        import subprocess
-        child_args = [a for a in sys.argv[1:] if a != "--no-cpu-baseline"] + ["--graph", "on", "--no-cpu-baseline"]
-        try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + child_args, env=dict(os.environ, NVFI_BENCH_CHILD="1"),
-                               stdout=subprocess.PIPE, text=True, timeout=900)
-            lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-            if r.returncode == 0 and lines:
-                graph_line = json.loads(lines[-1])
-            else:
-                print(f"bench.py: the hipGraph run failed (exit code {r.returncode}); measuring the eager step only", file=sys.stderr)
-        except subprocess.TimeoutExpired:
-            print("bench.py: the hipGraph run did not finish in 900 s; measuring the eager step only", file=sys.stderr)
+        # auto: report the faster launch mode of the same step.  The hipGraph replay takes the host out of the iteration - its time does not
+        # depend on the host's launch rate - while eager launches on three streams are ~3 % faster when the host keeps up (rocprof: the graph's
+        # branches start a little later).  Both modes run in this process after the setup: a short untimed pilot of each picks the mode, and
+        # only that mode runs the W warm-up and the K timed steps, so the time outside the timed steps does not grow with K.  (The graph's
+        # packet-capture fault, see above, stays off through DEBUG_CLR_GRAPH_PACKET_CAPTURE=0.)
         args.graph = "off"
+        auto_pick = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1182,16 +1241,44 @@ def main():
     if use_graph:
         run = GraphedStep(step)      # several ranks: three graphs around the eager exchange (GraphedStep._multi_iteration)
         run.capture()
+    launch_modes = None
+    if auto_pick:
+        # both modes advance the same iteration sequence (host draws, decays and Adam counters are shared), so the iterations that follow - and
+        # --dump-outputs - do not depend on which mode is picked
+        graphed = GraphedStep(step)
+        try:
+            graphed.capture()
+            pilot = {"eager_three_streams": [step, 0.0], "hipgraph_replay": [graphed, 0.0]}
+        except Exception as e:      # (a capture the runtime refuses: the eager step is still measured)
+            print(f"bench.py: the hipGraph capture failed ({e!r}); measuring the eager step only", file=sys.stderr)
+            pilot = {"eager_three_streams": [step, 0.0]}
+        for _ in range(PILOT_ROUNDS):
+            for e in pilot.values():
+                e[0]()                  # untimed: what a switch between the modes costs once (the first eager step after the replays can take ~0.3 s)
+                torch.cuda.synchronize()
+                tp = time.perf_counter()
+                for _ in range(PILOT_STEPS):
+                    e[0]()
+                torch.cuda.synchronize()
+                e[1] += (time.perf_counter() - tp) * 1e3 / (PILOT_ROUNDS * PILOT_STEPS)
+        use_graph = "hipgraph_replay" in pilot and pilot["hipgraph_replay"][1] < pilot["eager_three_streams"][1]
+        run = graphed if use_graph else step
+        launch_modes = {k: {"pilot_ms_per_step": e[1]} for k, e in pilot.items()}
+        launch_modes["timed"] = "hipgraph_replay" if use_graph else "eager_three_streams"
+        launch_modes["pilot"] = (f"{PILOT_ROUNDS} rounds x (1 + {PILOT_STEPS}) untimed steps of each mode, alternating, after the setup (the first step of each "
+                                 "block not counted); the K timed steps run the faster")
     for _ in range(args.warmup):         # the contract's W untimed warm-up steps
         run()
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        run()
+        last = run()
     barrier()
     dt = time.perf_counter() - t0
     if use_graph:
         run.check()
+    dump = step_outputs(step, last) if (args.dump_outputs and rank == 0) else None      # before the profiled pass steps again
     if world > 1:
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -1203,7 +1290,7 @@ def main():
 
     # ---- profiled pass (outside the timed region): HIP events around every launch of a kernel class on the launch stream, and the
     #      device-side work counters of those same steps
-    psteps = min(args.steps, 5) if args.profile_steps < 0 else args.profile_steps
+    psteps = (min(args.steps, 5) if args.full else 0) if args.profile_steps < 0 else args.profile_steps
     roof, work = None, None
     if psteps > 0:
         step.counters.clear(); step.pde_counters.clear()
@@ -1344,7 +1431,7 @@ def main():
     }
     if use_graph:
         out["config"]["graph_capture_attempts_ms"] = [round(x, 3) for x in run.capture_ms]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(model, args.workload, scene=scene)
         except Exception as e:  # the baseline is a report, never a reason to lose the bench line
@@ -1355,20 +1442,15 @@ def main():
                                         source=f"profiles/{PROFILE_TAG}_cpu_bridge.json (tools/cpu_bridge.py; /root/reference cannot run on the GPU box)")
     # Other lines of the same build, measured here so that they are recorded with the headline (each in its own process, same K / W, no
     # roofline pass); none of them is `value`.
-    default_invocation = (rank == 0 and world == 1 and args.mode == "fused" and args.workload == "cfg3" and scene == "bat" and not args.live and not args.no_extras
-                          and not os.environ.get("NVFI_BENCH_CHILD") and os.environ.get("NVFI_PDE_PREFILTER", "x6") == "x6")
+    default_invocation = (rank == 0 and world == 1 and args.mode == "fused" and args.workload == "cfg3" and scene == "bat" and not args.live and args.full
+                          and not args.no_extras and not os.environ.get("NVFI_BENCH_CHILD") and os.environ.get("NVFI_PDE_PREFILTER", "x6") == "x6")
     if default_invocation:
         from tools.bench_extras import collect      # (round 5: the extras live in tools/bench_extras.py)
         out["extras"] = collect(args, out, model)
-    if graph_line is not None:
-        modes = {"hipgraph_replay": {"value": graph_line["value"], "ms_per_step": graph_line["ms_per_step"]},
-                 "eager_three_streams": {"value": out["value"], "ms_per_step": out["ms_per_step"]}}
-        if graph_line["value"] > out["value"]:      # the child's line carries its own roofline pass; the CPU baseline was measured here
-            for k in ("cpu_baseline", "reference_cpu", "extras"):
-                if k in out:
-                    graph_line[k] = out[k]
-            out = graph_line
-        out["launch_modes"] = modes
+    if launch_modes is not None:
+        out["launch_modes"] = launch_modes
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

@@ -235,7 +235,8 @@ def test_bench_runs_as_two_ranks(scaling):
         scaling = "weak"
     port = 29700 + (os.getpid() % 1500) + (1 if scaling == "strong" else 0) + (2 if streams else 0)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "64", "--pts", "16384", "--prime", "1", "--no-cpu-baseline", "--scaling", scaling]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "64", "--pts", "16384", "--prime", "1", "--no-cpu-baseline", "--scaling", scaling,
+           "--full"]          # (work_per_step comes from the profiled pass)
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -1,8 +1,8 @@
 """tools/run_reference_driver.py: the reference's untouched training driver must import THIS repository's `models` (the script's own
 directory precedes PYTHONPATH, so a plain `python train_nvfi.py` would not), while `utils` / `datasets` stay the checkout's own; and the
 `TVLoss` object that driver builds from ITS `utils` package must stay on the fused regulariser kernel.  The checkout here is a decoy
-written by the test (a `models/` package that refuses to be imported, a `utils/` with a TVLoss look-alike, a driver script); when
-/root/reference exists (build container) the real checkout is resolved too."""
+written by the test (a `models/` package that refuses to be imported, a `utils/` with a TVLoss look-alike, a driver script)."""
+import importlib.util
 import json
 import os
 import subprocess
@@ -108,14 +108,21 @@ def test_tvloss_check_is_structural():
     assert not is_reference_tvloss(bad)
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/train_nvfi.py"), reason="the reference checkout exists in the build container only")
-def test_launcher_resolves_the_real_checkout():
-    r = subprocess.run([sys.executable, LAUNCHER, "--check", "--stub-missing", "/root/reference/train_nvfi.py"], capture_output=True, text=True)
+def test_launcher_resolves_a_reference_shaped_checkout(tmp_path):
+    """--check --stub-missing on a checkout laid out like the reference's: `utils` and `datasets` import optional third-party packages
+    (logging, metrics, image decoding) at import time; the launcher stubs the absent ones, resolves `models` to this repository's alias and
+    the other two packages to the checkout, and the TVLoss built from the checkout's `utils` stays on the fused kernel."""
+    co = _decoy(tmp_path, "import wandb\nfrom models import *\nfrom utils import *\nfrom datasets import *\n")
+    (co / "utils" / "__init__.py").write_text("import cv2\nimport lpips\nJET = cv2.COLORMAP_JET\n" + UTILS)
+    (co / "datasets" / "__init__.py").write_text("import imageio\nimport torchvision\nfrom torchvision import transforms\nWHO = 'checkout'\n")
+    r = subprocess.run([sys.executable, LAUNCHER, "--check", "--stub-missing", str(co / "train_nvfi.py")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-1500:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["resolved"]["models"] == os.path.join(ROOT, "models")
-    assert d["resolved"]["utils"] == "/root/reference/utils" and d["resolved"]["datasets"] == "/root/reference/datasets"
+    assert d["resolved"]["utils"] == str(co / "utils") and d["resolved"]["datasets"] == str(co / "datasets")
     assert d["reference_TVLoss_on_fused_kernel"] is True
+    absent = [n for n in ("wandb", "lpips", "imageio", "cv2", "torchvision", "torchvision.transforms") if importlib.util.find_spec(n.split(".")[0]) is None]
+    assert d["stubs"] == absent        # exactly the optional packages this host lacks, each registered as a stub
 
 
 @pytest.mark.gpu

@@ -24,7 +24,7 @@ def run_child(args, extra_args, env=None, steps_factor=1, scene_args=True, profi
     cmd = [sys.executable, script]
     if script == BENCH:
         cmd += ["--steps", str(args.steps * steps_factor), "--warmup", str(args.warmup * steps_factor),
-                "--profile-steps", "5" if (profile or full) else "0", "--no-extras"] + ([] if full else ["--no-cpu-baseline"])
+                "--profile-steps", "5" if (profile or full) else "0", "--no-extras"] + ([] if full else ["--no-cpu-baseline"]) + (["--full"] if (profile or full) else [])
         if scene_args:
             cmd += ["--rays", str(args.rays), "--pts", str(args.pts), "--grid", str(args.grid), "--samples", str(args.samples)]
     cmd += extra_args
