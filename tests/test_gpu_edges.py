@@ -252,13 +252,18 @@ def test_fused_mse_matches_torch(shape):
 def test_pde_gradients_add_up_over_ragged_point_sets(P):
     """The PDE term is a mean over the kept points, so n_kept * (value, gradient) of a point set equals the sum over any partition of it.  Checked for
     the shapes the persistent adjoint kernel (pde_fuse.hip) treats specially: a single 32-point tile, fewer tiles than workgroups, and more than one
-    262 144-point chunk (the second pass reuses stash, slabs and the tile queue) - each against its two ragged halves."""
-    model, meta = make_model("A")
+    262 144-point chunk (the second pass reuses stash, slabs and the tile queue) - each against its two ragged halves.  The chunks count KEPT
+    points: the two-chunk case runs on field B, which keeps every point of its box (field A keeps about a quarter of its central part)."""
+    two = P > 262144
+    model, meta = make_model("B" if two else "A")
     f = model.nvfi
     f.requires_grad_(True)
     g = torch.Generator(device="cuda").manual_seed(P)
     mn, mx = f.aabb
-    pts = torch.rand(P, 3, device="cuda", generator=g) * (mx - mn) * 0.6 + (mn + 0.2 * (mx - mn))      # around the occupied part of field A
+    if two:
+        pts = torch.rand(P, 3, device="cuda", generator=g) * (mx - mn) + mn
+    else:
+        pts = torch.rand(P, 3, device="cuda", generator=g) * (mx - mn) * 0.6 + (mn + 0.2 * (mx - mn))      # around the occupied part of field A
     tt = torch.rand(P, 1, device="cuda", generator=g)
     cut = P // 2 - 7
 
@@ -276,6 +281,8 @@ def test_pde_gradients_add_up_over_ragged_point_sets(P):
     n_a, a = term(slice(0, cut))
     n_b, b = term(slice(cut, P))
     assert n_all == n_a + n_b and n_all > (2 if P < 100 else 50), (n_all, n_a, n_b)
+    if two:
+        assert n_all > 262144, n_all       # the second pass does work
     parts = [x for x in (a, b) if x is not None]
     val = sum(x[0] for x in parts)
     grad = sum(x[1] for x in parts)
