@@ -887,12 +887,13 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_app_bwd(AppArgs a) {
 #define SCATTER_SPW 8
 __device__ __forceinline__ float dpp_xor1(float v) { return __shfl_xor(v, 1); }
 
-// DET: the gradient pointers address int64 shadow planes and every contribution is added as a fixed-point integer (2^50 per unit):
+// DET: the gradient pointers address int64 shadow planes and every contribution is added as a fixed-point integer (2^58 per unit):
 // integer addition is associative, so the sums are bit-identical whatever order the atomics arrive in (NVFI_DETERMINISTIC=1).
-#define DET_SCALE 1125899906842624.0      /* 2^50: +-8192 of range, 8.9e-16 of resolution */
+#define DET_SCALE 288230376151711744.0     /* 2^58: +-32 of range, 3.5e-18 of resolution (2^50 quantised the 1e-10 appearance-plane gradients of an
+                                              initial field at 2.5e-3 of their peak: tests/test_gpu_render64.py) */
 template <bool DET>
 __device__ __forceinline__ void grad_add(float* g, size_t idx, float v) {
-    // (a single contribution saturates at the int64 range instead of wrapping; running SUMS beyond +-8192 still wrap - test mode)
+    // (a single contribution saturates at the int64 range instead of wrapping; running SUMS beyond +-32 still wrap - test mode)
     if (DET) atomicAdd(reinterpret_cast<unsigned long long*>(g) + idx, (unsigned long long)__double2ll_rn(fmin(fmax((double)v * DET_SCALE, -9.2e18), 9.2e18)));
     else atomicAdd(g + idx, v);
 }

@@ -62,6 +62,45 @@ def named_grads(model):
     return out
 
 
+def field_state(model):
+    """(sd, meta) of a product NVFi module in the layout of the golden field fixtures: the reference-named parameters (numpy, without the `nvfi.`
+    prefix and the duplicated vel.vel_net keys) and the configuration scalars that reach the hot path.  Feeds oracle.FieldSpec and render64.Field."""
+    f = model.nvfi
+    sd = {k[len("nvfi."):]: v.detach().cpu().contiguous().numpy() for k, v in model.state_dict().items() if not k.startswith("nvfi.vel.vel_net.")}
+    sur, lo, hi = f._gate()
+    meta = dict(aabb=f.aabb.cpu().numpy(), gridSize=np.array(f.gridSize.tolist()), num_keyframes=f.num_keyframes, tmax=f.tmax,
+                near=f.near_far[0], far=f.near_far[1], step_ratio=f.step_ratio, max_n_samples=f.max_n_samples,
+                density_shift=f.density_shift, distance_scale=f.distance_scale, alphaMask_thres=f.alphaMask_thres,
+                rayMarch_weight_thres=f.rayMarch_weight_thres, stepSize=f._step_host, nSamples=f.nSamples, use_sur=int(sur))
+    if sur:
+        meta["sur_bounds"] = np.array([lo, hi], np.float32)
+    else:
+        meta["eps"] = float(f.vel.eps) if f.use_vel else 0.03
+    return sd, meta
+
+
+def select_rays(counts, target, usable=None, window=400):
+    """indices (ascending) of rays whose `counts` add up to exactly `target`, or None: rays are taken in order while more than `window` is
+    missing, then a subset-sum over the following rays closes the rest.  usable: bool per ray (rays that may be taken at all)."""
+    counts = np.asarray(counts, np.int64)
+    cand = np.arange(len(counts)) if usable is None else np.nonzero(np.asarray(usable))[0]
+    take, total, k = [], 0, 0
+    while k < len(cand) and target - total - counts[cand[k]] >= window:
+        take.append(int(cand[k])); total += int(counts[cand[k]]); k += 1
+    need = target - total
+    reach = {0: []}                       # sum -> rays (indices into cand), fewest rays first
+    for j in range(k, len(cand)):
+        c = int(counts[cand[j]])
+        if c == 0 or need in reach:
+            continue
+        for sm, rays in list(reach.items()):
+            if sm + c <= need and sm + c not in reach:
+                reach[sm + c] = rays + [int(cand[j])]
+    if need not in reach:
+        return None
+    return np.array(sorted(take + reach[need]), np.int64)
+
+
 def model_from_npz(z, prefix, device="cuda", use_vel=True):
     """Product NVFi module from a fixture that stores `<prefix>sd:*` / `<prefix>meta:*` arrays (tests/golden/r2.npz)."""
     from nvfi_amd.models import NVFi

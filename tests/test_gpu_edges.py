@@ -73,7 +73,8 @@ def test_transparent_field_keeps_no_pde_point():
 
 def test_largest_shipped_configuration():
     """199^3 grid, step_ratio 0.5, max_n_samples 1024 -> nSamples = 686: train fwd + bwd on a full 2048-ray chunk, finite
-    gradients everywhere, composite identities, and chunking invariance of the eval render."""
+    gradients everywhere, composite identities, and chunking invariance of the eval render.  (The values: tests/test_gpu_render64.py, case
+    big686, holds a 256-ray subset of this configuration to the float64 reference.)"""
     import bench
     from nvfi_amd.models import NVFi
     cfg = bench.bat_cfg(1024, True)

@@ -7,20 +7,14 @@ import pytest
 import torch
 
 from conftest import assert_grad
-from helpers import assert_contract, named_grads
+from helpers import assert_contract, field_state, named_grads
 
 pytestmark = pytest.mark.gpu
 
 
 def _field_spec(model):
     from oracle import oracle as orc
-    f = model.nvfi
-    sd = {k[len("nvfi."):]: v.detach().cpu().contiguous().numpy() for k, v in model.state_dict().items() if not k.startswith("nvfi.vel.vel_net.")}
-    meta = dict(aabb=f.aabb.cpu().numpy(), gridSize=np.array(f.gridSize.tolist()), num_keyframes=f.num_keyframes, tmax=f.tmax,
-                near=f.near_far[0], far=f.near_far[1], step_ratio=f.step_ratio, max_n_samples=f.max_n_samples,
-                density_shift=f.density_shift, distance_scale=f.distance_scale, alphaMask_thres=f.alphaMask_thres,
-                rayMarch_weight_thres=f.rayMarch_weight_thres, stepSize=f._step_host, nSamples=f.nSamples, use_sur=0, eps=0.03)
-    return orc.FieldSpec(sd, meta)
+    return orc.FieldSpec(*field_state(model))
 
 
 @pytest.fixture(scope="module")

@@ -51,14 +51,8 @@ def scene():
 
 def _field_spec(model):
     from oracle import oracle as orc
-    f = model.nvfi
-    sd = {k[len("nvfi."):]: v.detach().cpu().contiguous().numpy() for k, v in model.state_dict().items() if not k.startswith("nvfi.vel.vel_net.")}
-    sur = f.vel.bounds.detach().float().cpu().numpy().reshape(2, 3)      # normalised surround box (velocity_field.py:44)
-    meta = dict(aabb=f.aabb.cpu().numpy(), gridSize=np.array(f.gridSize.tolist()), num_keyframes=f.num_keyframes, tmax=f.tmax,
-                near=f.near_far[0], far=f.near_far[1], step_ratio=f.step_ratio, max_n_samples=f.max_n_samples,
-                density_shift=f.density_shift, distance_scale=f.distance_scale, alphaMask_thres=f.alphaMask_thres,
-                rayMarch_weight_thres=f.rayMarch_weight_thres, stepSize=f._step_host, nSamples=f.nSamples, use_sur=1, sur_bounds=sur)
-    return orc.FieldSpec(sd, meta)
+    from helpers import field_state
+    return orc.FieldSpec(*field_state(model))      # (the surround gate's normalised box, velocity_field.py:44, comes with it)
 
 
 @pytest.mark.parametrize("train", [False, True])
