@@ -1,6 +1,7 @@
 // abi.hip - error plumbing, version, self test and the small building-block entry points of the C ABI.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "common.h"
 #include "pde.h"
@@ -18,6 +19,25 @@ int nvfi_fail(int code, const char* fmt, ...) {
     return code;
 }
 extern "C" const char* nvfi_last_error(void) { return g_err; }
+
+// ---------------------------------------------------------------- environment switches (switches.h)
+static int parse_INT(Switch, const char* text) { return atoi(text); }
+static int parse_WORD(Switch s, const char* text) {
+    if (s == NVFI_SCATTER) return !strcmp(text, "lds") ? SCATTER_LDS : SCATTER_MFMA;
+    static const struct { const char* word; int value; } pre[] = {{"fp32", PRE_FP32}, {"split32", PRE_FP32}, {"x6", PRE_X6}, {"fp16band", PRE_FP16BAND}, {"split16band", PRE_SPLIT16BAND}};
+    for (const auto& p : pre) if (!strcmp(text, p.word)) return p.value;
+    return PRE_UNKNOWN;
+}
+int sw(Switch s) {
+    static std::once_flag once;
+    static int value[NVFI_SWITCH_COUNT];
+    std::call_once(once, [] {
+#define X(name, kind, def) { const char* e = getenv(#name); value[name] = parse_##kind(name, e ? e : #def); }
+        NVFI_SWITCHES(X)
+#undef X
+    });
+    return value[s];
+}
 extern "C" int nvfi_abi_version(void) { return NVFI_ABI_VERSION; }
 extern "C" int nvfi_stream_capture_id(void* stream, uint64_t* id) {
     hipStreamCaptureStatus stt = hipStreamCaptureStatusNone;
@@ -51,11 +71,7 @@ extern "C" int nvfi_vel_eval(const nvfi_field_desc* f, int64_t N, const float* x
 }
 
 // ---------------------------------------------------------------- integrate_pos (per-point times)
-static bool nograd_x6_default(const nvfi_field_desc* f) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("NVFI_INTEGRATE_X6"); on = e ? atoi(e) : 1; }
-    return on != 0 && !(f->vel_fp16 & 8);
-}
+static bool nograd_x6_default(const nvfi_field_desc* f) { return sw(NVFI_INTEGRATE_X6) != 0 && !(f->vel_fp16 & 8); }
 __global__ void k_pack_xt(int64_t N, const float* x, float4* xw) {
     int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i < N) xw[i] = make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], 0.f);
@@ -333,7 +349,8 @@ extern "C" int nvfi_selftest(float* max_err_host, void* stream) {
     P.W = dW; P.b = nullptr; P.frag = dF; P.bfrag = nullptr; P.out = O; P.in = K; P.MT = 4; P.NS = 64;
     P.row_kind = RK_NATURAL; P.slot_kind = SK_HIDDEN; P.transposed = 0; P.x4 = 0;
     if (launch_pack(jobs, st)) return 1;
-    HIPCK(hipFuncSetAttribute((const void*)k_selftest, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
+    static DeviceOnce once;
+    if (once.lds(ENGINE_LDS_BYTES, k_selftest)) return 1;
     hipLaunchKernelGGL(k_selftest, dim3(1), dim3(WG_THREADS), ENGINE_LDS_BYTES, st, dF, dW, dX, dO);
     LAUNCHCK();
     HIPCK(hipMemcpyAsync(hO, dO, O * J * 4, hipMemcpyDeviceToHost, st));

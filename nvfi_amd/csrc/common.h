@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../include/nvfi_hip.h"
 #include "engine.h"
+#include "switches.h"
 
 // ---------------------------------------------------------------- error plumbing (host)
 int nvfi_fail(int code, const char* fmt, ...);
@@ -16,24 +17,60 @@ int nvfi_fail(int code, const char* fmt, ...);
     } while (0)
 #define LAUNCHCK() HIPCK(hipGetLastError())
 
-// per-device one-time set-up of a launcher (hipFuncSetAttribute applies to the CURRENT device): `apply` runs under a lock until it has
-// succeeded once on the device - a failed or racing first call leaves nothing marked as done
-#ifdef __cplusplus
+// per-device one-time set-up of a launcher (hipFuncSetAttribute applies to the CURRENT device, and autograd runs backward nodes on per-device
+// worker threads): `apply` runs under a lock until it has succeeded once on the device - a failed or racing first call leaves nothing marked
+// as done.  Everything that is "once per device" in csrc/ goes through this struct; tests/test_abi_and_host.py keeps it so.
 #include <mutex>
+#define NVFI_MAX_DEVICES 64
+inline int device_slot() {                            // ordinal of the current device as an index of the per-device tables below
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NVFI_MAX_DEVICES) dev = 0;
+    return dev;
+}
 struct DeviceOnce {
     std::mutex mu;
-    bool done[64] = {false};
-    template <class F> int run(F apply) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    bool done[NVFI_MAX_DEVICES] = {false};
+    const char* file; int line;                       // where the object stands: an error names the launcher, not this header
+    DeviceOnce(const char* f = __builtin_FILE(), int l = __builtin_LINE()) : file(f), line(l) {}
+    template <class F> int run(F apply, int dev = device_slot()) {
         std::lock_guard<std::mutex> g(mu);
         if (done[dev]) return 0;
         const int rc = apply();
         if (rc == 0) done[dev] = true;
         return rc;
     }
+    // a launcher's attributes as data: `bytes` of dynamic LDS for every listed kernel
+    template <class... K> int lds(int bytes, K... kernels) {
+        return run([&] {
+            const void* k[] = {(const void*)kernels...};
+            for (int i = 0; i < (int)sizeof...(K); ++i) {
+                const hipError_t e = hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                if (e != hipSuccess) return nvfi_fail(100 + (int)e, "hipFuncSetAttribute(kernel %d of %d, hipFuncAttributeMaxDynamicSharedMemorySize, %d) failed: %s (%s:%d)",
+                                                      i + 1, (int)sizeof...(K), bytes, hipGetErrorString(e), file, line);
+            }
+            return 0;
+        });
+    }
 };
-#endif
+// one T per device, filled by init(T&, dev) -> 0 on the first call there; get() is the CURRENT device's (nullptr while init fails)
+template <class T> struct PerDevice {
+    DeviceOnce once;
+    T slot[NVFI_MAX_DEVICES];
+    PerDevice(const char* f = __builtin_FILE(), int l = __builtin_LINE()) : once(f, l), slot{} {}
+    template <class F> T* get(F init) {
+        const int dev = device_slot();
+        return once.run([&] { return init(slot[dev], dev); }, dev) ? nullptr : &slot[dev];
+    }
+};
+// number of CUs of the current device (256 where the runtime does not say): the grid of the persistent kernels
+inline int device_cu_count() {
+    static PerDevice<int> ncu;
+    return *ncu.get([](int& n, int dev) {
+        hipDeviceProp_t prop;
+        n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        return 0;
+    });
+}
 
 // optional per-kernel-class HIP-event timing (bench.py): events are recorded on the launch stream
 enum { PK_RK2_FWD = 0, PK_RK2_BWD, PK_APP_FWD, PK_APP_BWD, PK_WGRAD, PK_PDE_FWD, PK_PDE_BWD, PK_DENSITY_FWD, PK_DENSITY_BWD,
@@ -287,4 +324,3 @@ int launch_scan_fill(const int* cnt, int* off, int64_t ngroups, int* total, cons
 int launch_wgrad(const WgradJobs& wj, const ReduceJobs& rj, hipStream_t st);
 int launch_wgrad_ring(WgradJobs& bj, ReduceJobs& br, hipStream_t st);   // wgrad_ring.hip
 int ensure_lds_attrs();
-bool fused_launch();     // NVFI_FUSED_LAUNCH (default 1): round 5's fused small launches (render.hip)

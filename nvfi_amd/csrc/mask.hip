@@ -422,16 +422,8 @@ static int mask_frags16(const nvfi_mask_desc* m, float* frag, Mk16Frags* W, bool
 }
 
 static int mask_attrs() {
-    static bool done = false;
-    if (done) return 0;
-    HIPCK(hipFuncSetAttribute((const void*)k_maskfield_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_maskfield_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_maskfield_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_maskfield_fwd16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_maskfield_fwd16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_maskfield_bwd16, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    done = true;
-    return 0;
+    static DeviceOnce once;
+    return once.lds(ENGINE_LDS_BYTES, k_maskfield_fwd<true>, k_maskfield_fwd<false>, k_maskfield_bwd, k_maskfield_fwd16<true>, k_maskfield_fwd16<false>, k_maskfield_bwd16);
 }
 
 extern "C" int nvfi_maskfield_workspace_bytes(const nvfi_mask_desc* m, int64_t N, int train, int64_t* bytes) {

@@ -70,7 +70,7 @@ struct SplitArgs {
     const int* list; float4* xw;             // list[i] -> point index (NULL: identity); positions updated in place
     const float* pt_t; const float* pt_base; int pt_by_list; float dt_max; int max_steps;
 };
-int launch_rk2_split(const SplitArgs& a, int64_t cap_points, int wide, hipStream_t st);
+int launch_rk2_split(const SplitArgs& a, int64_t cap_points, hipStream_t st);
 // the render warp on the same layout (uniform step sequence, optional training stash)
 #define VEL_X4F_FLOATS (X4_FLOATS(4, 14) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(1, 64))     // forward fragments only
 struct SplitUniArgs { Rk2Args r; const float4* f4[6]; const float* bv[6]; };

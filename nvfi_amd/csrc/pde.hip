@@ -321,13 +321,6 @@ extern "C" int nvfi_pde_workspace_bytes(const nvfi_field_desc* f, int64_t P, int
     return 0;
 }
 
-static int ensure_pde_attrs() {
-    static bool done = false;
-    if (done) return 0;
-    done = true;
-    return 0;
-}
-
 static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* points, const float* t, float loss_scale, const float* loss_scale_dev,
                          float* out, const nvfi_grads* grads, void* workspace, int64_t workspace_bytes, int64_t* counters,
                          uint8_t* kept_out, float* jac_out, int64_t n_jac, int64_t* host_info, void* stream);
@@ -369,11 +362,11 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     if (P <= 0) return nvfi_fail(2, "P must be positive");
     if (P >= (1ll << 31) - 256) return nvfi_fail(2, "P too large");
     if (!f->use_vel) return nvfi_fail(2, "PDE loss needs use_vel");
-    if (ensure_pde_attrs() || ensure_lds_attrs()) return 1;
+    if (ensure_lds_attrs()) return 1;
     PdePlan L; plan_pde(P, workspace, &L);
     if (L.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld bytes, got %lld", (long long)L.total, (long long)workspace_bytes);
     if (launch_zero(L.cls_count, L.zero_bytes, st)) return 1;     // histogram / counts, loss sums, look-back words: one fill (a kernel, not hipMemsetAsync: common.h)
-    const bool fl = fused_launch();
+    const bool fl = sw(NVFI_FUSED_LAUNCH) != 0;
     PackJobs jobs; jobs.n = 0;
     VelFrags VW, AW;
     FragCache FC; const bool cached = f->frags != nullptr;       // round 5: the field's fragment cache (nvfi_pack_frags) instead of a repack per call
@@ -385,23 +378,17 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     // per (tile, column), NVFI_PDE_JET=0 - were retired in round 6.)
     // NVFI_PDE_FUSE (default 1): pde_fuse.hip - weight_net's Jacobian adjoint and its four 128 x 128 weight gradients in one persistent kernel
     // (no gz_1..gz_4 stash, no second pass over the z / zd stash); 0: k_pde_jet_bwd + k_wgrad_ring8 over the full adjoint stash
-    static int pde_fuse = -1;
-    if (pde_fuse < 0) { const char* e = getenv("NVFI_PDE_FUSE"); pde_fuse = e ? atoi(e) : 1; }
+    const int pde_fuse = sw(NVFI_PDE_FUSE);
     // prefilter mode: x6 (default, round 5: vel_x6.hip - the fp32 products of the hidden layers formed exactly on the 16-bit matrix pipe) | fp32 (the
     // feature-split fp32 MFMA kernel of vel_split.hip, the default of rounds 2-4; "engine32", k_rk2_fwd of vel.hip with the same numbers bit for
     // bit and ~4 % slower, was retired in round 6) | fp16band (pre16.hip: fp16-input pass + fp32 re-evaluation of the unsafe points)
     // split16band (opt-in, pre16.hip): the pre-pass with fp32 products emulated by two binary16 terms per operand (three fp16 MFMAs), and a
     // band 100 x narrower than fp16band's in front of the same fp32 re-evaluation
-    static int pre16 = -1; static float band16 = 0.1f, eps16 = 2e-3f;
-    if (pre16 < 0) {
-        const char* e = getenv("NVFI_PDE_PREFILTER");
-        if (e && strcmp(e, "fp16band") && strcmp(e, "split16band") && strcmp(e, "fp32") && strcmp(e, "split32") && strcmp(e, "x6"))
-            return nvfi_fail(2, "NVFI_PDE_PREFILTER must be fp32, x6, fp16band or split16band");
-        // 2 = split kernel ("split32" = "fp32"); 4 = x6 (vel_x6.hip: fp32 products formed exactly from three binary16 terms per operand)
-        // round 5: x6 is the default - its error against float64 is not larger than the fp32 MFMA kernel's (tests/test_gpu_x6.py) and it is 1.35x faster
-        pre16 = !e ? 4 : (!strcmp(e, "fp16band") ? 1 : (!strcmp(e, "split16band") ? 3 : (!strcmp(e, "x6") ? 4 : 2)));
-        if (pre16 == 3) { band16 = 1e-3f; eps16 = 2e-5f; }
-    }
+    // PRE_FP32 = split kernel ("split32" = "fp32"); PRE_X6 = x6 (vel_x6.hip: fp32 products formed exactly from three binary16 terms per operand)
+    // round 5: x6 is the default - its error against float64 is not larger than the fp32 MFMA kernel's (tests/test_gpu_x6.py) and it is 1.35x faster
+    const int pre16 = sw(NVFI_PDE_PREFILTER);
+    if (pre16 == PRE_UNKNOWN) return nvfi_fail(2, "NVFI_PDE_PREFILTER must be fp32, x6, fp16band or split16band");
+    const float band16 = pre16 == PRE_SPLIT16BAND ? 1e-3f : 0.1f, eps16 = pre16 == PRE_SPLIT16BAND ? 2e-5f : 2e-3f;
     const float4* f4[6] = {nullptr}; const float4* t4[6] = {nullptr};
     if (cached) { x4f_pointers(FC.vel_x4f, f4); x4b_pointers(FC.vel_x4b, t4); }
     else {
@@ -447,12 +434,12 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     SplitArgs sa; memset(&sa, 0, sizeof(sa));
     sa.f = *f; sa.xw = L.xw; sa.dt_max = ra.dt_max; sa.max_steps = PDE_MAX_CLASS;
     for (int l = 0; l < 6; ++l) { sa.f4[l] = f4[l]; sa.bv[l] = VW.b[l]; }
-    if (pre16 == 2) {
+    if (pre16 == PRE_FP32) {
         sa.count = nullptr; sa.n_direct = P; sa.list = L.perm; sa.pt_t = L.pt_t_perm; sa.pt_base = L.pt_base_perm;
-        if (launch_rk2_split(sa, P, 1, st)) return 1;
+        if (launch_rk2_split(sa, P, st)) return 1;
         da.n_direct = P; da.xw = L.xw;
         if (launch_density_q(da, P, st)) return 1;
-    } else if (pre16 == 4) {
+    } else if (pre16 == PRE_X6) {
         X6Args xa; memset(&xa, 0, sizeof(xa));
         xa.f = *f; xa.img = cached ? FC.vel_x6 : L.x6img; xa.n_direct = P; xa.list = L.perm; xa.xw = L.xw; xa.pt_t = L.pt_t_perm; xa.pt_base = L.pt_base_perm;
         xa.dt_max = ra.dt_max; xa.max_steps = PDE_MAX_CLASS;
@@ -463,7 +450,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     } else {
         // opt-in (pre16.hip): fp16-input pass over every candidate, then the fp32 kernel for the points whose decision is not safe
         Pre16Args qa; memset(&qa, 0, sizeof(qa));
-        qa.f = *f; qa.img = L.img16; qa.img_lo = pre16 == 3 ? L.img16lo : nullptr; qa.P = P; qa.list = L.perm; qa.xw = L.xw; qa.xout = L.xw16; qa.near = L.near;
+        qa.f = *f; qa.img = L.img16; qa.img_lo = pre16 == PRE_SPLIT16BAND ? L.img16lo : nullptr; qa.P = P; qa.list = L.perm; qa.xw = L.xw; qa.xout = L.xw16; qa.near = L.near;
         qa.pt_t = L.pt_t_perm; qa.pt_base = L.pt_base_perm; qa.dt_max = ra.dt_max; qa.max_steps = PDE_MAX_CLASS; qa.eps_gate = eps16;
         if (launch_pre16(f, qa, st)) return 1;
         da.n_direct = P; da.xw = L.xw16;
@@ -473,7 +460,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
         if (launch_pde_band_map(P, L.bcount, L.perm, L.blist, st)) return 1;
         // short list, long trajectories: the feature-split kernel (a tile's latency, not the chip's throughput, bounds this pass)
         sa.count = L.bcount; sa.list = L.blist; sa.pt_t = L.pt_t; sa.pt_base = L.pt_base; sa.pt_by_list = 1;
-        if (launch_rk2_split(sa, P, 0, st)) return 1;
+        if (launch_rk2_split(sa, P, st)) return 1;
         da.count = L.bcount; da.list = L.blist; da.xw = L.xw;
         if (launch_density_q(da, P, st)) return 1;
     }
@@ -524,10 +511,8 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
                 // all five weight_net columns of a tile in one workgroup; the ReLU acceleration net keeps its column kernel
                 // (the launch carries the acceleration net's value column as trailing workgroups: they fill the tail of the jet tiles)
                 // NVFI_PDE_JET_X6 (default 1, round 6): pde_jet6.hip - the same program with the hidden layers' products on the 16-bit matrix pipe
-                static int jet_x6 = -1;
-                if (jet_x6 < 0) { const char* e = getenv("NVFI_PDE_JET_X6"); jet_x6 = e ? atoi(e) : 1; }
-                if (jet_x6) {
-                    if (!cached && pre16 != 4 && first == 0 && launch_pack_x6(f->vW, L.x6img, st)) return 1;      // (the x6 prefilter has packed it already)
+                if (sw(NVFI_PDE_JET_X6)) {
+                    if (!cached && pre16 != PRE_X6 && first == 0 && launch_pack_x6(f->vW, L.x6img, st)) return 1;      // (the x6 prefilter has packed it already)
                     if (launch_pde_jet6_fwd(ja, cached ? FC.vel_x6 : L.x6img, (unsigned)(cap / TILE), wgs, st)) return 1;
                 } else if (launch_pde_jet_fwd(ja, (unsigned)(cap / TILE), wgs, st)) return 1;
             }
@@ -536,7 +521,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
                 const bool last_pass = first + L.chunk >= P;
                 ja.tail.ticket = L.cls_count + PDE_MAX_CLASS + 2; ja.tail.dcount = grads ? L.dcount : nullptr;
                 ja.tail.out = last_pass ? out : nullptr;
-                ja.tail.counters = last_pass ? counters : nullptr; ja.tail.cls_count = L.cls_count; ja.tail.P = P; ja.tail.pre16 = (pre16 == 1 || pre16 == 3) ? 1 : 0;
+                ja.tail.counters = last_pass ? counters : nullptr; ja.tail.cls_count = L.cls_count; ja.tail.P = P; ja.tail.pre16 = (pre16 == PRE_FP16BAND || pre16 == PRE_SPLIT16BAND) ? 1 : 0;
                 if (last_pass) finished = true;
             }
             hipLaunchKernelGGL(k_pde_seeds, dim3((unsigned)(cap / 256 + 1)), dim3(256), 0, st, ja);
@@ -572,9 +557,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
                     // half (tiles from a device-side queue); otherwise the acceleration net's adjoint keeps k_pde_jet_bwd's trailing workgroups
                     fa.do_accel = (grads->aW[1] && grads->aW[2] && grads->aW[3] && grads->aW[4]) ? 1 : 0;
                     fa.slabs_a = fused_slabs_a;
-                    static int det = -1;
-                    if (det < 0) { const char* e = getenv("NVFI_DETERMINISTIC"); det = (e && atoi(e) != 0) ? 1 : 0; }
-                    fa.queue = det ? nullptr : L.dcount + 8;
+                    fa.queue = sw(NVFI_DETERMINISTIC) ? nullptr : L.dcount + 8;
                     if (!fa.do_accel && launch_pde_jet_bwd(ja, 0, wgs, sb)) return 1;
                     // a split call (the reference's loop: the caller waits for the value - `if loss_vel > 0` - while this half runs on the other
                     // stream) leaves 8 CUs to the caller's comparison / copy kernels: a persistent workgroup owns its CU, and behind 256 of them
@@ -593,7 +576,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     if (!finished) hipLaunchKernelGGL(k_pde_finish, dim3(1), dim3(64), 0, st, L.sums, L.kcount, out);
     LAUNCHCK();
     if (counters && !fl) {
-        hipLaunchKernelGGL(k_pde_counters, dim3(1), dim3(64), 0, st, L.cls_count, L.kcount, P, pre16 == 1 || pre16 == 3, counters);
+        hipLaunchKernelGGL(k_pde_counters, dim3(1), dim3(64), 0, st, L.cls_count, L.kcount, P, pre16 == PRE_FP16BAND || pre16 == PRE_SPLIT16BAND, counters);
         LAUNCHCK();
     }
     return 0;

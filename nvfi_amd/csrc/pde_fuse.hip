@@ -621,17 +621,9 @@ int launch_pde_fuse_bwd(const PdeFuseArgs& a, int64_t cap_points, int max_slabs,
     *nslab_out = 0;
     const int64_t tiles = (cap_points + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
-    static int ncu_dev[64] = {0};                          // per device: the attribute and the CU count belong to the current device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!ncu_dev[dev]) {
-        hipDeviceProp_t prop;
-        int n = 256;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
-        HIPCK(hipFuncSetAttribute((const void*)k_pde_fuse_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS_BYTES));
-        ncu_dev[dev] = n;
-    }
-    const int ncu = ncu_dev[dev];
+    static DeviceOnce once;
+    if (once.lds(PF_LDS_BYTES, k_pde_fuse_bwd)) return 1;
+    const int ncu = device_cu_count();
     int G = ncu < max_slabs ? ncu : max_slabs;           // one persistent workgroup per CU (leaving 8-32 CUs to the other streams: no gain)
     if ((int64_t)G > tiles) G = (int)tiles;
 #ifdef PF_TIMING

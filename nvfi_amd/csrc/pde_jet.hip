@@ -363,12 +363,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_pde_jet_bwd(PdeJetArgs a) {
 }
 
 int ensure_jet_attrs() {
-    static bool done = false;
-    if (done) return 0;
-    HIPCK(hipFuncSetAttribute((const void*)k_pde_jet_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, JET_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_pde_jet_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, JET_LDS_BYTES));
-    done = true;
-    return 0;
+    static DeviceOnce once;
+    return once.lds(JET_LDS_BYTES, k_pde_jet_fwd, k_pde_jet_bwd);
 }
 int launch_pde_jet_fwd(const PdeJetArgs& a0, unsigned tiles, unsigned anet_wgs, hipStream_t st) {
     if (ensure_jet_attrs()) return 1;

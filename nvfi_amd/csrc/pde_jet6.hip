@@ -275,7 +275,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
 
 int launch_pde_jet6_fwd(const PdeJetArgs& a0, const void* x6img, unsigned tiles, unsigned anet_wgs, hipStream_t st) {
     static DeviceOnce once;
-    if (once.run([] { HIPCK(hipFuncSetAttribute((const void*)k_pde_jet6_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, J6_LDS_BYTES)); return 0; })) return 1;
+    if (once.lds(J6_LDS_BYTES, k_pde_jet6_fwd)) return 1;
     PdeJetArgs a = a0; a.jet_tiles = (int)tiles;
     hipLaunchKernelGGL(k_pde_jet6_fwd, dim3(tiles + anet_wgs), dim3(WG_THREADS), J6_LDS_BYTES, st, a, reinterpret_cast<const b8_t*>(x6img));
     LAUNCHCK();

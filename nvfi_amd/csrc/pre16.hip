@@ -300,15 +300,8 @@ __global__ __launch_bounds__(P16_THREADS, 1) void k_rk2_inf16(Rk16Args a) {
 }
 
 int launch_rk2_inf16(const nvfi_field_desc* f, Rk16Args a, bool uniform, hipStream_t st, bool stash) {
-    static bool attr = false;
-    if (!attr) {
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_inf16<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_inf16<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_inf16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_inf16<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_inf16<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        attr = true;
-    }
+    static DeviceOnce once;
+    if (once.lds(PRE16_IMAGE_BYTES, k_rk2_inf16<true, false, true>, k_rk2_inf16<true, false>, k_rk2_inf16<false, false>, k_rk2_inf16<true, true>, k_rk2_inf16<false, true>)) return 1;
     if (a.P <= 0) return 0;
     const bool split = !stash && (f->vel_fp16 & 3) == 2;      // two binary16 terms per operand (fp32 products emulated): the lo image follows the hi image
     a.img_lo = split ? (char*)a.img + PRE16_IMAGE_BYTES : nullptr;
@@ -352,12 +345,8 @@ __global__ __launch_bounds__(256) void k_pde_band(nvfi_field_desc f, int64_t P, 
 }
 
 int launch_pre16(const nvfi_field_desc* f, Pre16Args a, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_pre16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_pre16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PRE16_IMAGE_BYTES));
-        attr = true;
-    }
+    static DeviceOnce once;
+    if (once.lds(PRE16_IMAGE_BYTES, k_rk2_pre16<false>, k_rk2_pre16<true>)) return 1;
     Pack16VelArgs pk;
     for (int l = 0; l < 6; ++l) { pk.W[l] = f->vW[l]; pk.b[l] = f->vb[l]; }
     pk.img = reinterpret_cast<h8_t*>(a.img);

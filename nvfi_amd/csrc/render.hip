@@ -147,14 +147,7 @@ __global__ __launch_bounds__(256) void k_fill(int64_t R, int S, const uint8_t* _
 // the training warp's kernel family and what it means for the stash layout (forward and backward must agree, so both ask here):
 // NVFI_RK2_X6 (default 1): the x6 kernels; NVFI_RK2_FUSE (default 1): the adjoint + hidden-layer weight gradients in one persistent kernel - then the z
 // rows of layers 0..3 have ONE reader and travel as x4 stash blocks (a quarter of the stash instructions on both sides; NVFI_RK2_X4=0: row-major)
-static bool warp_x6_on() { static int v = -1; if (v < 0) { const char* e = getenv("NVFI_RK2_X6"); v = e ? atoi(e) : 1; } return v != 0; }
-static bool rk2_fuse_on() { static int v = -1; if (v < 0) { const char* e = getenv("NVFI_RK2_FUSE"); v = e ? atoi(e) : 1; } return v != 0; }
-static bool warp_stash_x4(const nvfi_field_desc* f) {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("NVFI_RK2_X4"); v = e ? atoi(e) : 1; }
-    return v != 0 && warp_x6_on() && rk2_fuse_on() && !(f->vel_fp16 & 4);
-}
-bool fused_launch() { static int u = -1; if (u < 0) { const char* e = getenv("NVFI_FUSED_LAUNCH"); u = e ? atoi(e) : 1; } return u != 0; }
+static bool warp_stash_x4(const nvfi_field_desc* f) { return sw(NVFI_RK2_X4) && sw(NVFI_RK2_X6) && sw(NVFI_RK2_FUSE) && !(f->vel_fp16 & 4); }
 
 // k_sample + the two k_fill launches behind it
 __global__ __launch_bounds__(256) void k_sample_fill(SampleArgs a) {
@@ -1096,21 +1089,6 @@ __global__ __launch_bounds__(1024) void k_plane_scatter_lds(ScatterArgs a) {
 // pipes idle, so the backward can fork them next to the weight-gradient / RK2-adjoint kernels and join before returning.
 // Off by default: it gained 2.5 % while those kernels ran two workgroups per CU, but since they own a CU each (one wave per
 // SIMD with the whole register file, engine.h: FragPipe) a scatter wave cannot co-reside with them and the fork only splits CUs.
-struct SideStream {
-    hipStream_t s = nullptr; hipEvent_t fork[2] = {nullptr, nullptr}, join = nullptr; int state = -1;
-    int get() {
-        if (state >= 0) return state;
-        const char* e = getenv("NVFI_SIDE_STREAM");
-        state = (e && atoi(e) != 0) ? 1 : 0;
-        if (state) {
-            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) state = 0;
-            for (int i = 0; i < 2 && state; ++i) if (hipEventCreateWithFlags(&fork[i], hipEventDisableTiming) != hipSuccess) state = 0;
-            if (state && hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess) state = 0;
-        }
-        return state;
-    }
-};
-static SideStream g_side;
 // NVFI_BWD_FORK (flags bit 16), for a caller that drives ONE stream: parts of the render backward run on a library-owned stream, with their
 // own tile-sort workspace / slab region, joined before the call returns.
 //   keyframe time: the two halves - appearance (k_app_bwd, k_og<48>, tile scatter, render-MLP weight gradients) and density (k_weights_bwd,
@@ -1118,36 +1096,23 @@ static SideStream g_side;
 //   non-keyframe time: the coordinate gradients chain k_app_bwd -> k_og<48> -> k_og<24> -> RK2 adjoint -> velocity-net weight gradients; the
 //     plane scatters of both branches and the render-MLP weight gradients hang off that chain and run beside it.
 // A caller that already overlaps several renders / the PDE term on its own streams (bench.py's fused driver) leaves the bit off.
-struct ForkStream {
-    hipStream_t s = nullptr; hipEvent_t fork = nullptr, fork2 = nullptr, join = nullptr; int state = -1;
-    std::once_flag once;
-    int get() {
-        // created on the device that is current at the first call, once (autograd runs backward nodes on per-device worker threads)
-        std::call_once(once, [this] {
-            int st = 1;
-            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) st = 0;
-            if (st && hipEventCreateWithFlags(&fork, hipEventDisableTiming) != hipSuccess) st = 0;
-            if (st && hipEventCreateWithFlags(&fork2, hipEventDisableTiming) != hipSuccess) st = 0;
-            if (st && hipEventCreateWithFlags(&join, hipEventDisableTiming) != hipSuccess) st = 0;
-            state = st;
-        });
-        return state;
-    }
-};
-// one fork stream per device ordinal: a second device (or a second field on another device) in the same process gets its own stream and
-// events instead of launching its forked half on the first device's
-#define NVFI_MAX_DEVICES 16
-static ForkStream g_forks[NVFI_MAX_DEVICES];
-static ForkStream& fork_of_current_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NVFI_MAX_DEVICES) dev = 0;
-    return g_forks[dev];
+// Both are library-owned streams with their fork / join events, one set per device ordinal: a second device (or a second field on another
+// device) in the same process gets its own instead of launching its forked half on the first device's.  Created on the first call on the
+// device (autograd runs backward nodes on per-device worker threads); a creation that fails is remembered and leaves the caller on one stream.
+struct LibStream { hipStream_t s; hipEvent_t fork[2], join; bool ok; };
+static PerDevice<LibStream> g_sides, g_forks;
+static LibStream* lib_stream(PerDevice<LibStream>& per) {
+    LibStream* l = per.get([](LibStream& n, int) {
+        n.ok = hipStreamCreateWithFlags(&n.s, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&n.fork[0], hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&n.fork[1], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&n.join, hipEventDisableTiming) == hipSuccess;
+        return 0;
+    });
+    return l->ok ? l : nullptr;
 }
-#define g_fork (fork_of_current_device())
 
 // NVFI_DETERMINISTIC=1: bit-reproducible plane gradients for tests.  The sorted-tile path sums in an order that
 // depends on atomic cursors; this mode takes the plain atomic scatter instead and accumulates in fixed point (k_plane_scatter<C, true>).
-static bool det_mode() { static int d = -1; if (d < 0) { const char* e = getenv("NVFI_DETERMINISTIC"); d = (e && atoi(e) != 0) ? 1 : 0; } return d != 0; }
+static bool det_mode() { return sw(NVFI_DETERMINISTIC) != 0; }
 static int64_t plane_elems(const nvfi_field_desc* f, int64_t* off /* [12]: dps[3] dpt[3] aps[3] apt[3] */) {
     const int A[3] = {0, 0, 1}, Bx[3] = {1, 2, 2}, Cc[3] = {2, 1, 0};
     int64_t n = 0;
@@ -1170,12 +1135,8 @@ static int launch_scatter(const nvfi_field_desc* f, ScatterArgs& sa, int C, int6
     gmax = gmax > f->G[2] ? gmax : f->G[2];
     const size_t lds = (size_t)6 * gmax * 24 * sizeof(float);
     if (lds <= 150 * 1024) {
-        static bool attr = false;
-        if (!attr) {
-            HIPCK(hipFuncSetAttribute((const void*)k_plane_scatter_lds<24>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-            HIPCK(hipFuncSetAttribute((const void*)k_plane_scatter_lds<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-            attr = true;
-        }
+        static DeviceOnce once;
+        if (once.lds(152 * 1024, k_plane_scatter_lds<24>, k_plane_scatter_lds<48>)) return 1;
         // row y0 of the time planes: same arithmetic as bl_setup on the per-call time coordinate
         const float y = (tn + 1.f) * ((float)(f->K - 1) / 2.f);
         float yf = floorf(y);
@@ -1343,7 +1304,6 @@ struct RenderPlan {
 #define NSLAB 256            // slab capacity of a weight-gradient job (one per CU; the NVFI_NSLAB sweep of round 2 was retired in round 6)
 #define SLAB_FLOATS (128 * 128 + 128)
 
-static bool use_tiles() { static int u = -1; if (u < 0) { const char* e = getenv("NVFI_SCATTER_TILES"); u = e ? atoi(e) : 1; } return u != 0; }
 static void plan_render(const nvfi_field_desc* f, int64_t R, int flags, int nsteps, void* ws, RenderPlan* P) {
     Bump B{(char*)ws, 0, 0};
     const int64_t N = R * f->n_samples;
@@ -1354,7 +1314,7 @@ static void plan_render(const nvfi_field_desc* f, int64_t R, int flags, int nste
     P->counters = B.take<int>(16);
     // the histograms (+ tickets) of the backward's two counting sorts sit right behind the counters: the forward's one fill zeroes all
     // three (the scans re-zero the histograms after every use, so the backward needs no fill of its own)
-    P->tiles = train && tile_geom(f, &P->tw.g) == 0 && use_tiles() && !det_mode();
+    P->tiles = train && tile_geom(f, &P->tw.g) == 0 && sw(NVFI_SCATTER_TILES) && !det_mode();
     P->tw.hist = P->tw2.hist = nullptr;
     if (P->tiles) { P->tw2.g = P->tw.g; P->tw.hist = B.take<int>(P->tw.g.nbins + 64); P->tw2.hist = B.take<int>(P->tw.g.nbins + 64); }
     // ... and so do the look-back words of the two fused compactions (k_sample_fill, k_weights_fill): one per workgroup of 4 rays
@@ -1427,14 +1387,8 @@ extern "C" int nvfi_render_workspace_bytes_t(const nvfi_field_desc* f, int64_t R
 }
 
 static int ensure_render_attrs() {
-    static bool done = false;
-    if (done) return 0;
-    HIPCK(hipFuncSetAttribute((const void*)k_app_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_app_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_app_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    if (ensure_scatter_attrs()) return 1;
-    done = true;
-    return 0;
+    static DeviceOnce once;
+    return once.lds(ENGINE_LDS_BYTES, k_app_fwd<true>, k_app_fwd<false>, k_app_bwd) || ensure_scatter_attrs();
 }
 
 extern "C" int nvfi_render_fwd(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d,
@@ -1478,7 +1432,7 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
     const int S = f->n_samples;
     const int64_t N = P.N;
     const float tn = f->use_vel ? norm_time(*f, base) : norm_time(*f, t);
-    const bool fl = fused_launch();
+    const bool fl = sw(NVFI_FUSED_LAUNCH) != 0;
     const bool pro = fl && R <= PROLOGUE_MAX_RAYS;      // one-workgroup prologue: clear + schedule + origin test
     const float* sched = nullptr;
     if (t_dev && nsteps > 4) return nvfi_fail(2, "a device-side time supports plans of up to 4 RK2 steps (t=%g needs %d)", t, nsteps);
@@ -1540,7 +1494,7 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
         // round 5: the warp on the x6 evaluation (vel_x6.hip: the hidden layers' fp32 products formed exactly from three bfloat16 terms per operand
         // on the 16-bit matrix pipe; same stash / records for the fp32 adjoint) unless NVFI_RK2_X6=0 or an fp16-input mode is asked for
         const int vf = f->vel_fp16 & 3;
-        if ((warp_x6_on() && !(train && (f->vel_fp16 & 4)) && (train || vf == 0 || vf == 3)) || (!train && vf == 3)) {
+        if ((sw(NVFI_RK2_X6) && !(train && (f->vel_fp16 & 4)) && (train || vf == 0 || vf == 3)) || (!train && vf == 3)) {
             ra.z_x4 = (train && warp_stash_x4(f)) ? 1 : 0;
             X6UniArgs xa; xa.r = ra; xa.img = cached ? FC.vel_x6 : P.x6img;
             if (!cached && launch_pack_x6(f->vW, P.x6img, st)) return 1;
@@ -1633,17 +1587,19 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
     const float tn = f->use_vel ? norm_time(*f, base) : norm_time(*f, t);
     const float* sched = t_on_device ? P.sched : nullptr;     // the record the forward's k_sched left in the workspace
     const unsigned ray_blocks = (unsigned)((R + 3) / 4);
-    const bool side = g_side.get() != 0 && !P.tiles && !det_mode();   // the tile scatter reuses one og buffer for both branches: same stream
+    LibStream* const sides = sw(NVFI_SIDE_STREAM) ? lib_stream(g_sides) : nullptr;
+    const bool side = sides && !P.tiles && !det_mode();        // the tile scatter reuses one og buffer for both branches: same stream
     const bool want_aplanes0 = grads->aps[0] || grads->apt[0], want_dplanes0 = grads->dps[0] || grads->dpt[0];
-    const bool forkable = (flags & NVFI_BWD_FORK) && P.tiles && want_aplanes0 && want_dplanes0 && !det_mode() && g_fork.get() != 0;
+    LibStream* const forks = ((flags & NVFI_BWD_FORK) && P.tiles && want_aplanes0 && want_dplanes0 && !det_mode()) ? lib_stream(g_forks) : nullptr;
+    const bool forkable = forks != nullptr;
     const bool fork = forkable && nsteps == 0, fork2 = forkable && nsteps > 0;
     hipStream_t sd = st;                                     // stream of k_weights_bwd / k_og<24> (keyframe fork: the side stream)
     hipStream_t s_atail = st, s_dtail = st;                  // streams of the appearance tail (scatter, render-MLP weight gradients) and of the density scatter
-    if (fork) { sd = g_fork.s; s_dtail = g_fork.s; }
-    if (fork2) { s_atail = g_fork.s; s_dtail = g_fork.s; }
+    if (fork) { sd = forks->s; s_dtail = forks->s; }
+    if (fork2) { s_atail = forks->s; s_dtail = forks->s; }
     // round 5: both counting sorts of the backward (masked list -> P.tw, valid list -> P.tw2) in ONE pair of launches, up front - the lists and the
     // positions are the forward's; the density branch then always sorts into tw2 and keeps sharing the og buffer unless it runs on the side stream
-    const bool fl = fused_launch();
+    const bool fl = sw(NVFI_FUSED_LAUNCH) != 0;
     const bool want_asort = P.tiles && want_aplanes0, want_dsort = P.tiles && want_dplanes0;
     const bool presort = fl && (want_asort || want_dsort);
     TileWork twd_v = (fork || fork2 || presort) ? P.tw2 : P.tw;
@@ -1656,7 +1612,7 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
         ProfScope ps(PK_DENSITY_SCATTER, st);
         if (launch_tile_sort(wp, cp, lp, nj, P.xw, N, st)) return 1;
     }
-    if (fork) { HIPCK(hipEventRecord(g_fork.fork, st)); HIPCK(hipStreamWaitEvent(g_fork.s, g_fork.fork, 0)); }     // (behind the sorts)
+    if (fork) { HIPCK(hipEventRecord(forks->fork[0], st)); HIPCK(hipStreamWaitEvent(forks->s, forks->fork[0], 0)); }     // (behind the sorts)
     // deterministic mode: the scatters add fixed-point integers into int64 shadow planes; k_det_finish folds them into the gradients
     nvfi_grads gdet = *grads;
     int64_t det_off[12]; int64_t det_n = 0;
@@ -1696,7 +1652,7 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
             oa.f = *f; oa.count = P.counters + 1; oa.list = P.mlist; oa.xw = P.xw; oa.tn = tn; oa.sched = sched; oa.gg = P.gg; oa.og = want_aplanes ? P.tw.og : nullptr;
             oa.gxw_acc = nsteps > 0 ? P.gxw : nullptr;
             if (launch_og(f, oa, 48, nsteps > 0, N, st)) return 1;
-            if (fork2) { HIPCK(hipEventRecord(g_fork.fork, st)); HIPCK(hipStreamWaitEvent(g_fork.s, g_fork.fork, 0)); }
+            if (fork2) { HIPCK(hipEventRecord(forks->fork[0], st)); HIPCK(hipStreamWaitEvent(forks->s, forks->fork[0], 0)); }
             if (want_aplanes) {
                 if (launch_tile_scatter(f, P.tw, P.counters + 1, P.mlist, P.xw, tn, *grads, 48, N, s_atail, sched, presort)) return 1;
             }
@@ -1705,7 +1661,7 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
         ScatterArgs sa; memset(&sa, 0, sizeof(sa));
         sa.f = *f; sa.count = P.counters + 1; sa.list = P.mlist; sa.xw = P.xw; sa.tn = tn; sa.sched = sched; sa.gg = P.gg; sa.g = det_mode() ? gdet : *grads; sa.plane_mask = 63;
         hipStream_t ss = st;
-        if (side) { HIPCK(hipEventRecord(g_side.fork[0], st)); HIPCK(hipStreamWaitEvent(g_side.s, g_side.fork[0], 0)); ss = g_side.s; forked = true; }
+        if (side) { HIPCK(hipEventRecord(sides->fork[0], st)); HIPCK(hipStreamWaitEvent(sides->s, sides->fork[0], 0)); ss = sides->s; forked = true; }
         ProfScope ps(PK_APP_SCATTER, ss);
         if (det_mode() ? launch_scatter_det(sa, 48, N, ss) : launch_scatter(f, sa, 48, N, tn, ss)) return 1;
     }
@@ -1756,18 +1712,18 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
             oa.mflag = P.mflag; oa.gxw = P.gxw; oa.gxk = nsteps > 0 ? P.gxk : nullptr;
             if (launch_og(f, oa, 24, nsteps > 0, N, sd)) return 1;
         }
-        if (fork2) { HIPCK(hipEventRecord(g_fork.fork2, st)); HIPCK(hipStreamWaitEvent(g_fork.s, g_fork.fork2, 0)); }
+        if (fork2) { HIPCK(hipEventRecord(forks->fork[1], st)); HIPCK(hipStreamWaitEvent(forks->s, forks->fork[1], 0)); }
         if (want_dplanes) {
             ProfScope ps(PK_DENSITY_SCATTER, s_dtail);
             if (launch_tile_scatter(f, twd, P.counters + 0, P.vlist, P.xw, tn, *grads, 24, N, s_dtail, sched, presort)) return 1;
         }
-        if (fork) { HIPCK(hipEventRecord(g_fork.join, g_fork.s)); HIPCK(hipStreamWaitEvent(st, g_fork.join, 0)); }
+        if (fork) { HIPCK(hipEventRecord(forks->join, forks->s)); HIPCK(hipStreamWaitEvent(st, forks->join, 0)); }
     } else if (nsteps > 0) { ProfScope ps(PK_DENSITY_BWD, st); hipLaunchKernelGGL(k_density_bwd, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, da); }
     if (!P.tiles && want_dplanes) {
         ScatterArgs sa; memset(&sa, 0, sizeof(sa));
         sa.f = *f; sa.count = P.counters + 0; sa.list = P.vlist; sa.xw = P.xw; sa.tn = tn; sa.sched = sched; sa.gxpre = P.gxpre; sa.g = det_mode() ? gdet : *grads; sa.plane_mask = 63;
         hipStream_t ss = st;
-        if (side) { HIPCK(hipEventRecord(g_side.fork[1], st)); HIPCK(hipStreamWaitEvent(g_side.s, g_side.fork[1], 0)); ss = g_side.s; forked = true; }
+        if (side) { HIPCK(hipEventRecord(sides->fork[1], st)); HIPCK(hipStreamWaitEvent(sides->s, sides->fork[1], 0)); ss = sides->s; forked = true; }
         ProfScope ps(PK_DENSITY_SCATTER, ss);
         if (det_mode() ? launch_scatter_det(sa, 24, N, ss) : launch_scatter(f, sa, 24, N, tn, ss)) return 1;
     }
@@ -1791,7 +1747,7 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
         ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles; ra.gxk = P.gxk;
         // NVFI_RK2_FUSE (default 1): vel_fuse.hip - the adjoint AND the four 128 x 128 weight gradients in one persistent kernel (no g_1..g_4
         // stash, no second pass over the z stash); 0: k_rk2_split_bwd + k_wgrad_ring8 over the full adjoint stash
-        const int fuse = rk2_fuse_on() ? 1 : 0;
+        const int fuse = sw(NVFI_RK2_FUSE) ? 1 : 0;
         ra.z_x4 = warp_stash_x4(f) ? 1 : 0;                              // (what the forward wrote: the same predicate)
         float* vslabs = (fork2 || merge_wgrad) ? P.slabs2 : P.slabs;      // (merged launches: the render MLP's slabs in P.slabs are still live)
         int fused_nslab = 0;
@@ -1814,8 +1770,8 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
         if (launch_vel_wgrad(P.zst, P.x0st, P.gst, P.counters + 3, (int)P.cap_tiles, 2 * nsteps, BM_SILU, vslabs, NSLAB,
                              grads->vW, grads->vb, 1.f, st, fused_nslab, merge_wgrad ? &mlp_wj : nullptr, merge_wgrad ? &mlp_rj : nullptr)) return 1;
     }
-    if (fork2) { HIPCK(hipEventRecord(g_fork.join, g_fork.s)); HIPCK(hipStreamWaitEvent(st, g_fork.join, 0)); }
-    if (forked) { HIPCK(hipEventRecord(g_side.join, g_side.s)); HIPCK(hipStreamWaitEvent(st, g_side.join, 0)); }
+    if (fork2) { HIPCK(hipEventRecord(forks->join, forks->s)); HIPCK(hipStreamWaitEvent(st, forks->join, 0)); }
+    if (forked) { HIPCK(hipEventRecord(sides->join, sides->s)); HIPCK(hipStreamWaitEvent(st, sides->join, 0)); }
     return 0;
 }
 
@@ -2028,8 +1984,8 @@ extern "C" int nvfi_render_mask(const nvfi_field_desc* f, const nvfi_mask_desc* 
     RenderPlan P;
     plan_render(f, R, flags, nsteps < 0 ? 0 : nsteps, workspace, &P);
     if (P.total > workspace_bytes) return nvfi_fail(4, "workspace too small");
-    static bool attr = false;
-    if (!attr) { HIPCK(hipFuncSetAttribute((const void*)k_mask_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES)); attr = true; }
+    static DeviceOnce once;
+    if (once.lds(ENGINE_LDS_BYTES, k_mask_fwd)) return 1;
     if (!P.mask_frag) return nvfi_fail(2, "nvfi_render_mask needs a workspace planned with NVFI_WANT_MASK in flags");
     float* frag = P.mask_frag;
     PackJobs jobs; jobs.n = 0;

@@ -719,7 +719,6 @@ __global__ __launch_bounds__(64 * MS_WAVES) void k_tile_scatter_mfma(TileScatter
 
 // ---------------------------------------------------------------- host
 // NVFI_SCATTER=mfma (default) | lds: the MFMA kernel on 4x4-texel tiles, or the LDS read-add-write kernel on 8x8-texel tiles
-static bool scatter_mfma() { static int u = -1; if (u < 0) { const char* e = getenv("NVFI_SCATTER"); u = (e && !strcmp(e, "lds")) ? 0 : 1; } return u != 0; }
 static int tile_geom_T(const nvfi_field_desc* f, TileGeom* g, int T, int chunk) {
     const int ia[3] = {0, 0, 1}, ib[3] = {1, 2, 2};
     int off = 0;
@@ -734,7 +733,7 @@ static int tile_geom_T(const nvfi_field_desc* f, TileGeom* g, int T, int chunk) 
     return off;
 }
 int tile_geom(const nvfi_field_desc* f, TileGeom* g) {
-    if (scatter_mfma() && tile_geom_T(f, g, SCATTER_T_MFMA, SCATTER_CHUNK_MFMA) <= SCATTER_MAX_BINS_MFMA) return 0;
+    if (sw(NVFI_SCATTER) == SCATTER_MFMA && tile_geom_T(f, g, SCATTER_T_MFMA, SCATTER_CHUNK_MFMA) <= SCATTER_MAX_BINS_MFMA) return 0;
     return tile_geom_T(f, g, SCATTER_T, SCATTER_CHUNK) <= SCATTER_MAX_BINS ? 0 : 1;
 }
 
@@ -757,11 +756,8 @@ void plan_tile_scatter(Bump& B, const nvfi_field_desc* f, int64_t N, TileWork* w
 
 // k_tile_hist's scan uses up to 70 KB of dynamic LDS (8192 bins): raised once, from the entry points (never inside a stream capture)
 int ensure_scatter_attrs() {
-    static bool done = false;
-    if (done) return 0;
-    HIPCK(hipFuncSetAttribute((const void*)k_tile_hist, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    done = true;
-    return 0;
+    static DeviceOnce once;
+    return once.lds(80 * 1024, k_tile_hist);
 }
 
 int launch_og(const nvfi_field_desc* f, const OgArgs& oa, int C, bool coord, int64_t N, hipStream_t st) {

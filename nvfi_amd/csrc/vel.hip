@@ -104,13 +104,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_fwd(Rk2Args a) {
 
 // ---------------------------------------------------------------- host-side helpers
 int ensure_lds_attrs() {
-    static bool done = false;
-    if (done) return 0;
-    HIPCK(hipFuncSetAttribute((const void*)k_vel_eval, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_rk2_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    HIPCK(hipFuncSetAttribute((const void*)k_rk2_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ENGINE_LDS_BYTES));
-    done = true;
-    return 0;
+    static DeviceOnce once;
+    return once.lds(ENGINE_LDS_BYTES, k_vel_eval, k_rk2_fwd<true>, k_rk2_fwd<false>);
 }
 
 int launch_vel_eval(const VelEvalArgs& a, hipStream_t st) {

@@ -840,23 +840,11 @@ int launch_rk2_fuse_bwd(const FuseBwdArgs& a, int64_t cap_samples, int max_slabs
     *nslab_out = 0;
     const int64_t tiles = (cap_samples + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
-    // per device: the dynamic-LDS attribute and the CU count belong to the device that is current at the call
-    static int ncu_dev[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!ncu_dev[dev]) {
-        hipDeviceProp_t prop;
-        int n = 256;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_fuse_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSE_LDS_BYTES));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_fuse_bwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FUSE_LDS_BYTES_X6));
-        ncu_dev[dev] = n;
-    }
+    static DeviceOnce once, once_x6;
+    if (once.lds(FUSE_LDS_BYTES, k_rk2_fuse_bwd<false>) || once_x6.lds(FUSE_LDS_BYTES_X6, k_rk2_fuse_bwd<true>)) return 1;
     // NVFI_FUSE_X6 (default 1, round 6): the adjoint waves' dgrad on the 16-bit matrix pipe (fuse_velnet_bwd_x6); 0: the fp32 MFMA dgrad of round 4
-    static int x6 = -1;
-    if (x6 < 0) { const char* e = getenv("NVFI_FUSE_X6"); x6 = e ? atoi(e) : 1; }
-    const bool use_x6 = x6 != 0 && a.imgT != nullptr;
-    const int ncu = ncu_dev[dev];
+    const bool use_x6 = sw(NVFI_FUSE_X6) != 0 && a.imgT != nullptr;
+    const int ncu = device_cu_count();
     int G = ncu < max_slabs ? ncu : max_slabs;           // one persistent workgroup per CU: 12 waves x 168 registers (leaving CUs to the other streams: no gain)
     if ((int64_t)G > tiles) G = (int)tiles;
     ProfScope ps(PK_RK2_BWD, st);

@@ -630,28 +630,15 @@ int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t
     return 0;
 }
 
-// wide = 0: one tile per workgroup (shortest latency: short lists); wide = 1: NVFI_SPLIT_NT tiles per workgroup share every weight load
-int launch_rk2_split(const SplitArgs& a, int64_t cap_points, int wide, hipStream_t st) {
+// One tile per workgroup, the output layer on the vector pipe.  (Until round 6 a switch, NVFI_SPLIT_NT, put two or four tiles of a long list into
+// one workgroup: alone one tile is 1.5 % slower than two (1.32 against 1.30 ms; every weight load feeds one tile), but its 130-register
+// workgroups leave the render chains' kernels more room beside it - the three-stream step is 1 % faster (5.04 against 5.10 ms).)
+int launch_rk2_split(const SplitArgs& a, int64_t cap_points, hipStream_t st) {
     const int64_t tiles = (cap_points + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
     ProfScope ps(PK_PDE_PREFILTER, st);
-    static int nt = -1, vout = 1;
-    if (nt < 0) {
-        // NVFI_SPLIT_NT: tiles per workgroup of the wide launch.  With the output layer on the vector pipe one tile is the default: alone it is
-        // 1.5 % slower than two (1.32 against 1.30 ms; every weight load feeds one tile), but its 130-register workgroups leave the render
-        // chains' kernels more room beside it - the three-stream step is 1 % faster (5.04 against 5.10 ms).  NVFI_SPLIT_VOUT=0: matrix pipe.
-        nt = 1; vout = 1;
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_split<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_VOUT_LDS_BYTES(4)));
-        HIPCK(hipFuncSetAttribute((const void*)k_rk2_split<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_VOUT_LDS_BYTES(4)));
-    }
-    const int n = wide ? nt : 1;
-    const dim3 b(WG_THREADS);
-    // (both variants get the larger LDS image of the vector-pipe form: three workgroups per CU either way)
-#define SPLIT_GO(NT_) do { const dim3 g((unsigned)((tiles + NT_ - 1) / NT_));                                                              \
-        if (vout) hipLaunchKernelGGL((k_rk2_split<NT_, true>), g, b, SPLIT_VOUT_LDS_BYTES(NT_), st, a);                                   \
-        else hipLaunchKernelGGL((k_rk2_split<NT_, false>), g, b, SPLIT_VOUT_LDS_BYTES(NT_), st, a); } while (0)
-    if (n == 1) SPLIT_GO(1); else if (n == 4) SPLIT_GO(4); else SPLIT_GO(2);
-#undef SPLIT_GO
+    hipLaunchKernelGGL((k_rk2_split<1, true>), dim3((unsigned)tiles), dim3(WG_THREADS), SPLIT_VOUT_LDS_BYTES(1), st, a);
     LAUNCHCK();
     return 0;
 }
+template __global__ void k_rk2_split<1, false>(SplitArgs);   // (the output layer on the matrix pipe: no launcher since NVFI_SPLIT_VOUT went, kept in the library)

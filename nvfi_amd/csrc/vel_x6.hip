@@ -446,25 +446,17 @@ __global__ __launch_bounds__(WG_THREADS, NT == 1 ? 2 : 1) void k_rk2_x6_uni(X6Un
 // waves per SIMD: all clean).  Asking for more than half of the CU's LDS keeps a second workgroup off the CU - the other
 // configuration known to be clean (about 7 % of the step slower; the switch for it, NVFI_X6_ONE_WG, was retired in round 6).
 #define X6_ONE_WG_LDS (84 * 1024)
-// (per device: hipFuncSetAttribute applies to the device that is current - one process per GPU never sees a second one, a host that drives
-// several devices from one process does)
-template <typename K>
-static int x6_set_lds(K kernel) {
-    HIPCK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X6_ONE_WG_LDS));
-    return 0;
-}
 static size_t x6_lds_nt1() { return (size_t)X6_LDS_BYTES(1); }      // (NVFI_X6_ONE_WG=1 asked for X6_ONE_WG_LDS here: retired in round 6, the fence in build.py is the fix)
 
 int launch_rk2_x6_uni(const X6UniArgs& a, int64_t cap_samples, bool stash, hipStream_t st) {
     const int64_t tiles = (cap_samples + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
     static DeviceOnce once;
-    if (once.run([] { return (x6_set_lds(k_rk2_x6_uni<1, true, true>) || x6_set_lds(k_rk2_x6_uni<1, true>) || x6_set_lds(k_rk2_x6_uni<1, false>)) ? 1 : 0; })) return 1;
+    if (once.lds(X6_ONE_WG_LDS, k_rk2_x6_uni<1, true, true>, k_rk2_x6_uni<1, true>, k_rk2_x6_uni<1, false>)) return 1;
     ProfScope ps(PK_RK2_FWD, st);
     // NVFI_X6W_UNI: 1 (default) eval renders on the one-wave-per-tile kernel of vel_x6w.hip (bit-identical; an 800 x 800 test frame 134 -> 120 ms),
     // 2 training renders too (same stash and records; no faster there: 0.35 against 0.37 ms, the stash stores are not hidden), 0 neither
-    static int wuni = -1;
-    if (wuni < 0) { const char* e = getenv("NVFI_X6W_UNI"); wuni = e ? atoi(e) : 1; }
+    const int wuni = sw(NVFI_X6W_UNI);
     if ((wuni >= 1 && !stash) || wuni >= 2) return launch_rk2_x6w_uni(a, cap_samples, stash, st);
     // (round 6: the two-tiles-per-workgroup variants - NVFI_X6_NT=2 - are retired: never a default, 8 % slower)
     if (stash && a.r.z_x4) hipLaunchKernelGGL((k_rk2_x6_uni<1, true, true>), dim3((unsigned)tiles), dim3(WG_THREADS), x6_lds_nt1(), st, a);
@@ -478,19 +470,15 @@ int launch_rk2_x6(const X6Args& a, int64_t cap_points, hipStream_t st) {
     const int64_t tiles = (cap_points + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
     static DeviceOnce once;
-    if (once.run([] { return x6_set_lds(k_rk2_x6<1>) ? 1 : 0; })) return 1;
+    if (once.lds(X6_ONE_WG_LDS, k_rk2_x6<1>)) return 1;
     // default since round 5 (late): one wave per tile, the epilogue in the MFMAs' VALU slots (vel_x6w.hip; bit-identical results, the bench
     // prefilter 0.89 -> 0.83 ms).  NVFI_X6W=0: the four-waves-per-tile kernel below
-    static int x6w = -1;
-    if (x6w < 0) { const char* e = getenv("NVFI_X6W"); x6w = e ? atoi(e) : 1; }
     // round 6: a SMALL call is latency-bound - its evaluations are a serial chain per tile, 60 k cycles each on one wave (x6w) against ~17.5 k with
     // the tile's four row tiles on four SIMDs (k_rk2_x6<1>; 35 k with two workgroups per CU) - so up to NVFI_X6W_MIN_TILES the four-wave kernel
     // runs; same products in the same order, identical bits (tests/test_gpu_x6.py).  Default 4096, measured on the PDE prefilter (trajectories of up
     // to 20 evaluations): 1024 tiles (the strong-scaling shard) 0.41 -> 0.19 ms, 4096 tiles 0.45 -> 0.44 ms, 8192 tiles (the full batch) one wave per
     // tile wins (0.80 against 0.89 ms).  train_segm's integrate_pos (3 000-30 000 occupied points, 40-60 evaluations deep): 1.03 -> 0.46 ms.
-    static int min_tiles = -1;
-    if (min_tiles < 0) { const char* e = getenv("NVFI_X6W_MIN_TILES"); min_tiles = e ? atoi(e) : 4096; }
-    if (x6w && tiles > min_tiles) return launch_rk2_x6w(a, cap_points, st);
+    if (sw(NVFI_X6W) && tiles > sw(NVFI_X6W_MIN_TILES)) return launch_rk2_x6w(a, cap_points, st);
     hipLaunchKernelGGL(k_rk2_x6<1>, dim3((unsigned)tiles), dim3(WG_THREADS), x6_lds_nt1(), st, a);
     LAUNCHCK();
     return 0;

@@ -273,15 +273,10 @@ static int ring_slot_bytes(const WgradJob& J) {
 // on return (bj / br are updated; the caller launches k_wgrad_reduce over br).
 int launch_wgrad_ring(WgradJobs& bj, ReduceJobs& br, hipStream_t st) {
     if (bj.n == 0) return 0;
-    static int ncu = 0, want = 0;
-    if (!ncu) {
-        int dev = 0; hipDeviceProp_t prop;
-        ncu = 256;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
-        want = ncu;                                             // workgroups of a launch: one per CU (192 of 256 measured +1.5 % in round 3, within noise since)
-        HIPCK(hipFuncSetAttribute((const void*)k_wgrad_ring8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    int G = want, lds_need = 68 * 1024;                         // (the end-of-job exchange of the two sample halves needs 66.5 KB)
+    static DeviceOnce once;
+    if (once.lds(160 * 1024, k_wgrad_ring8)) return 1;
+    // workgroups of a launch: one per CU (192 of 256 measured +1.5 % in round 3, within noise since)
+    int G = device_cu_count(), lds_need = 68 * 1024;            // (the end-of-job exchange of the two sample halves needs 66.5 KB)
     for (int i = 0; i < bj.n; ++i) {
         const WgradJob& J = bj.j[i];
         const bool ok = (J.a_regs == 64 && J.b_regs == 64) || (J.a_regs == 16 && J.b_regs == 64) || (J.a_regs == 64 && J.b_regs == 16 && J.bmode == BM_RAW) ||

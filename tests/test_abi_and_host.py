@@ -241,3 +241,30 @@ def test_ray_lazy_buffers_follow_the_module_and_camera_attributes_are_assignable
     rays = cam.rays
     cam.rays = rays; cam.coords = cam.coords                   # attributes in the reference, assignable here too
     assert cam.rays is rays
+
+
+def test_switch_table_matches_the_integration_guide_and_is_the_only_reader():
+    """csrc/switches.h is the one table of the environment variables the library reads: INTEGRATION section 4 shows the same default for every
+    row, abi.hip's reader is the only getenv of csrc/, and the per-device set-up of a launcher goes through common.h's DeviceOnce (text only)."""
+    csrc = os.path.join(ROOT, "nvfi_amd", "csrc")
+    rows = re.findall(r"^\s*X\((NVFI_\w+),\s*(INT|WORD),\s*(\w+)\)", open(os.path.join(csrc, "switches.h")).read(), flags=re.M)
+    assert len(rows) == 16 and len({name for name, _, _ in rows}) == 16, rows
+    guide = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = guide[guide.index("## 4. Environment switches of the library"):]
+    documented = {}
+    for line in section.splitlines():
+        cells = [c.strip() for c in line.split("|")]
+        if len(cells) < 4 or not cells[1].startswith("`NVFI_"):
+            continue
+        names, defaults = re.findall(r"`(NVFI_\w+)`", cells[1]), re.findall(r"`([^`]*)`", cells[2])
+        if len(names) == len(defaults):             # (a row may list two variables: `A`, `B` | `1`, `1`)
+            documented.update(zip(names, defaults))
+    for name, _, default in rows:
+        assert documented.get(name) == default, f"{name}: switches.h says {default}, INTEGRATION section 4 says {documented.get(name)}"
+    sources = {fn: open(os.path.join(csrc, fn), errors="ignore").read() for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h"))}
+    assert [fn for fn, txt in sources.items() if "getenv" in txt] == ["abi.hip"]
+    assert sources["abi.hip"].count("getenv") == 1
+    old_idiom = {fn: [w for w in ("static bool done", "static bool attr", "hipFuncSetAttribute") if w in txt and (fn, w) != ("common.h", "hipFuncSetAttribute")]
+                 for fn, txt in sources.items()}
+    old_idiom = {fn: w for fn, w in old_idiom.items() if w}
+    assert not old_idiom, old_idiom
