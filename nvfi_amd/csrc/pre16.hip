@@ -185,8 +185,7 @@ __global__ __launch_bounds__(P16_THREADS, 1) void k_rk2_pre16(Pre16Args a) {
     for (int s = 0; s < a.max_steps; ++s) {
         const bool live = fabsf(off) > 0.f;
         if (!__any(live)) break;
-        const float m = fminf(fabsf(off), a.dt_max);
-        const float dt = off > 0.f ? m : (off < 0.f ? -m : 0.f);
+        const float dt = rk2_point_dt(off, a.dt_max);
         float o4[4], w1[6], w2[6], v1[3], v2[3];
         velnet16<SPLIT>(W, Wlo, bias, lane, h, make_float4(x, y, z, tcur), o4);
         gather6(o4, h, w1);
@@ -256,8 +255,7 @@ __global__ __launch_bounds__(P16_THREADS, 1) void k_rk2_inf16(Rk16Args a) {
         else {
             live = fabsf(off) > 0.f;
             if (!__any(live)) break;
-            const float m = fminf(fabsf(off), a.dt_max);
-            dt = off > 0.f ? m : (off < 0.f ? -m : 0.f);
+            dt = rk2_point_dt(off, a.dt_max);
         }
         float o4[4], w1[6], w2[6], v1[3], v2[3];
         float *z1 = nullptr, *z2 = nullptr, *x1 = nullptr, *x2 = nullptr;

@@ -69,8 +69,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_fwd(Rk2Args a) {
         else {
             bool unfinished = fabsf(off) > 0.f;
             if (!__syncthreads_or(unfinished)) break;
-            float m = fminf(fabsf(off), a.dt_max);
-            dt = off > 0.f ? m : (off < 0.f ? -m : 0.f);
+            dt = rk2_point_dt(off, a.dt_max);
         }
         const bool live = active && (UNIFORM || fabsf(off) > 0.f);
         float o4[4], w1[6], w2[6], v1[3], v2[3];

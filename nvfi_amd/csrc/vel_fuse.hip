@@ -6,7 +6,7 @@
 // step, and two kernels that each own the matrix pipe at ~0.5 of its peak.  Here ONE persistent workgroup of TWELVE waves per CU does both:
 //
 //   * waves 0-3 ("adjoint" waves, one per SIMD, raised priority) run the dgrad chain of one 32-sample tile exactly like
-//     k_rk2_split_bwd<1>: wave w owns rows [32w, 32w+32) of every layer's input gradient, x4 transposed fragments from L2 into registers;
+//     the one-tile form of k_rk2_split_bwd: wave w owns rows [32w, 32w+32) of every layer's input gradient, x4 transposed fragments from L2 into registers;
 //     the layer gradients g_l AND the layer inputs a_l = SiLU(z_l) (the sigmoid is shared with SiLU') go to LDS in the exchange layout,
 //     XOR-swizzled so that the same image serves the dgrad's B operand (one 16-byte read per four K steps, a lane = a sample) and the
 //     weight gradient's operands (a lane = a feature row, one 4-byte read per K step, conflict-free);

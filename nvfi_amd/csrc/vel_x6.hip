@@ -42,58 +42,11 @@ int launch_pack_x6(const float* const* W, void* img, hipStream_t st, void* imgT)
     return 0;
 }
 
-// ---------------------------------------------------------------- three-term split of 8 activations -> the B operands of one K step
-// By TRUNCATION (NVFI_X6_ROUND_SPLIT undefined): t1 = the upper 16 bits of x, r = x - t1 (<= 16 significant bits, exact), t2 = the upper 16
-// bits of r, t3 = r - t2 (<= 8 significant bits: its upper 16 bits ARE the value) - x = t1 + t2 + t3 exactly, like the rounded split the
-// weights get at pack time (x6.h split3), for 3 v_perm_b32 + 4 v_and_b32 + 4 v_sub_f32 per PAIR of values instead of 6 conversions, 4 shifts
-// / masks and 4 subtractions: the epilogue is VALU time the matrix pipe waits for.  The terms are up to twice as large as rounded ones
-// (|t2| < 2^-7 |x|, |t3| < 2^-15 |x|), so the three dropped term products (w2 x3, w3 x2, w3 x3: < 2^-22 of the product) are too; the error
-// against float64 stays at the fp32 kernels' (tests/test_gpu_x6.py).
-__device__ __forceinline__ void split3_8(const float* v, b8_t& b1, b8_t& b2, b8_t& b3) {
-#ifdef NVFI_X6_ROUND_SPLIT
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 t1, t2, t3;
-        split3(v[j], t1, t2, t3);
-        b1[j] = t1; b2[j] = t2; b3[j] = t3;
-    }
-#else
-    unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float xa = v[2 * j], xb = v[2 * j + 1];
-        const unsigned ua = __float_as_uint(xa), ub = __float_as_uint(xb);
-        p1[j] = __builtin_amdgcn_perm(ub, ua, 0x07060302u);                       // (upper half of xb) << 16 | upper half of xa
-        const float ra = xa - __uint_as_float(ua & 0xffff0000u), rb = xb - __uint_as_float(ub & 0xffff0000u);
-        const unsigned va = __float_as_uint(ra), vb = __float_as_uint(rb);
-        p2[j] = __builtin_amdgcn_perm(vb, va, 0x07060302u);
-        const float sa = ra - __uint_as_float(va & 0xffff0000u), sb = rb - __uint_as_float(vb & 0xffff0000u);
-        p3[j] = __builtin_amdgcn_perm(__float_as_uint(sb), __float_as_uint(sa), 0x07060302u);
-    }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 q1 = {p1[0], p1[1], p1[2], p1[3]}, q2 = {p2[0], p2[1], p2[2], p2[3]}, q3 = {p3[0], p3[1], p3[2], p3[3]};
-    b1 = __builtin_bit_cast(b8_t, q1); b2 = __builtin_bit_cast(b8_t, q2); b3 = __builtin_bit_cast(b8_t, q3);
-#endif
-}
-
-// the six term products of one K step for one tile: a0 += A1 B1 (the leading terms: the sum the fp32 MFMA forms, in the same order) ;
-// a1 += A1 B2 + A2 B2 + A2 B1 + A1 B3 + A3 B1 (everything <= 2^-8 of it: rounding among these is 2^-32 of the result).  Two accumulators since
-// round 5 late (three before: a separate one for the 2^-16 class bought nothing measurable and cost 16 registers and 16 adds per drain)
-__device__ __forceinline__ void x6_step(const b8_t& A1, const b8_t& A2, const b8_t& A3, const b8_t& B1, const b8_t& B2, const b8_t& B3,
-                                        f32x16& a0, f32x16& a1) {
-    a0 = MFMA16B(A1, B1, a0);
-    a1 = MFMA16B(A1, B2, a1);
-    a1 = MFMA16B(A2, B2, a1);
-    a1 = MFMA16B(A2, B1, a1);
-    a1 = MFMA16B(A1, B3, a1);
-    a1 = MFMA16B(A3, B1, a1);
-}
-
 // LDS exchange image of one tile: [term][K step 0..7][lane] h8
 #define X6_XCH_H8 (3 * 8 * 64)
 #define X6_LDS_BYTES(NT) ((NT) * (X6_XCH_H8 * 16 + 4 * 2 * 32 * 16) + 6 * 128 * 4 + 4 * 2 * 16 * 8 * 4)
 
-// one gated-velocity network evaluation of the workgroup's NT tiles (velnet_split_vout of vel_split.hip with x6 hidden layers)
+// one gated-velocity network evaluation of the workgroup's NT tiles (velnet_split_vout of vel_split.hip with x6 hidden layers; NT is 1 in every kernel that is built)
 //
 // Schedule of one layer: the tile's whole layer input (8 K steps x 3 terms = 24 operands, 96 registers) is read from LDS, the A operands
 // (weights) rotate through four register sets refilled from L2 behind the MFMAs of a later step, and the layer ends with the drain - the
@@ -124,8 +77,8 @@ __device__ __forceinline__ void velnet_x6(const b8_t* __restrict__ img, b8_t* xc
             float x0[16];
             vel_encode_slots(q[t], h, x0);
             if (STASH && w == t) stash_store<16>(x0st[t], lane, x0);
-            split3_8(x0, Bf[t][0][0], Bf[t][0][1], Bf[t][0][2]);
-            split3_8(x0 + 8, Bf[t][1][0], Bf[t][1][1], Bf[t][1][2]);
+            x6_split8(x0, Bf[t][0][0], Bf[t][0][1], Bf[t][0][2]);
+            x6_split8(x0 + 8, Bf[t][1][0], Bf[t][1][1], Bf[t][1][2]);
             // one register tuple per operand, alive until the pin behind the drain
 #pragma unroll
             for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(Bf[t][s][0]), "+v"(Bf[t][s][1]), "+v"(Bf[t][s][2]));
@@ -136,7 +89,7 @@ __device__ __forceinline__ void velnet_x6(const b8_t* __restrict__ img, b8_t* xc
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) x6_step(A1[s], A2[s], A3[s], Bf[t][s][0], Bf[t][s][1], Bf[t][s][2], a0[t], a1[t]);
+            for (int t = 0; t < NT; ++t) x6_mm6(A1[s], A2[s], A3[s], Bf[t][s][0], Bf[t][s][1], Bf[t][s][2], a0[t], a1[t]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
@@ -180,7 +133,7 @@ __device__ __forceinline__ void velnet_x6(const b8_t* __restrict__ img, b8_t* xc
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 b8_t b1, b2, b3;
-                split3_8(v[t] + 8 * k, b1, b2, b3);
+                x6_split8(v[t] + 8 * k, b1, b2, b3);
                 b8_t* dst = xch + (size_t)t * X6_XCH_H8 + (2 * w + k) * 64 + lane;
                 dst[0] = b1; dst[8 * 64] = b2; dst[16 * 64] = b3;
             }
@@ -198,7 +151,7 @@ __device__ __forceinline__ void velnet_x6(const b8_t* __restrict__ img, b8_t* xc
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t) x6_step(A1[s & 3], A2[s & 3], A3[s & 3], Bf[t][s][0], Bf[t][s][1], Bf[t][s][2], a0[t], a1[t]);
+            for (int t = 0; t < NT; ++t) x6_mm6(A1[s & 3], A2[s & 3], A3[s & 3], Bf[t][s][0], Bf[t][s][1], Bf[t][s][2], a0[t], a1[t]);
             __builtin_amdgcn_sched_barrier(0);
             if (s + 3 < 8) { A1[(s + 3) & 3] = P1[(s + 3) * 64]; A2[(s + 3) & 3] = P2[(s + 3) * 64]; A3[(s + 3) & 3] = P3[(s + 3) * 64]; }
             __builtin_amdgcn_sched_barrier(0);
@@ -266,7 +219,7 @@ __device__ __forceinline__ void velnet_x6(const b8_t* __restrict__ img, b8_t* xc
     }
 }
 
-// the recurrence of k_rk2_split<NT, true> (vel_split.hip), per-point times
+// the recurrence of k_rk2_split (vel_split.hip), per-point times
 template <int NT>
 __global__ __launch_bounds__(WG_THREADS, NT == 1 ? 2 : 1) void k_rk2_x6(X6Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -306,8 +259,7 @@ __global__ __launch_bounds__(WG_THREADS, NT == 1 ? 2 : 1) void k_rk2_x6(X6Args a
         for (int t = 0; t < NT; ++t) {
             live[t] = active[t] && fabsf(off[t]) > 0.f;
             any = any || live[t];
-            const float m = fminf(fabsf(off[t]), a.dt_max);
-            dt[t] = off[t] > 0.f ? m : (off[t] < 0.f ? -m : 0.f);
+            dt[t] = rk2_point_dt(off[t], a.dt_max);
         }
         if (!__any(any)) break;                           // the same decision in all four waves (replicated state)
         float o6[NT][6], px[NT], py[NT], pz[NT];
@@ -345,7 +297,7 @@ __global__ __launch_bounds__(WG_THREADS, NT == 1 ? 2 : 1) void k_rk2_x6(X6Args a
 }
 
 // ---------------------------------------------------------------- render warp: every sample takes the same (dt_s, t_s) sequence
-// (rk2_split_uni_body of vel_split.hip on the x6 evaluation: same compact list, same in-place update, same stash and records)
+// (k_rk2_split_uni of vel_split.hip on the x6 evaluation: same compact list, same in-place update, same stash and records)
 template <int NT, bool STASH, bool X4 = false>
 __global__ __launch_bounds__(WG_THREADS, NT == 1 ? 2 : 1) void k_rk2_x6_uni(X6UniArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -444,24 +396,21 @@ __global__ __launch_bounds__(WG_THREADS, NT == 1 ? 2 : 1) void k_rk2_x6_uni(X6Un
 // the speed is the same (the epilogues hide behind the other workgroup's MFMAs).  The mechanism is NOT understood: none of the pieces
 // reproduces in isolation (tools/probes/mfma_hazard_probe.hip, nine experiments incl. packed fp32 beside this MFMA pattern at 1, 2 and 4
 // waves per SIMD: all clean).  Asking for more than half of the CU's LDS keeps a second workgroup off the CU - the other
-// configuration known to be clean (about 7 % of the step slower; the switch for it, NVFI_X6_ONE_WG, was retired in round 6).
-#define X6_ONE_WG_LDS (84 * 1024)
-static size_t x6_lds_nt1() { return (size_t)X6_LDS_BYTES(1); }      // (NVFI_X6_ONE_WG=1 asked for X6_ONE_WG_LDS here: retired in round 6, the fence in build.py is the fix)
+// configuration known to be clean (about 7 % of the step slower); the fence in build.py is the fix.
 
 int launch_rk2_x6_uni(const X6UniArgs& a, int64_t cap_samples, bool stash, hipStream_t st) {
     const int64_t tiles = (cap_samples + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
     static DeviceOnce once;
-    if (once.lds(X6_ONE_WG_LDS, k_rk2_x6_uni<1, true, true>, k_rk2_x6_uni<1, true>, k_rk2_x6_uni<1, false>)) return 1;
+    if (once.lds(X6_LDS_BYTES(1), k_rk2_x6_uni<1, true, true>, k_rk2_x6_uni<1, true>, k_rk2_x6_uni<1, false>)) return 1;
     ProfScope ps(PK_RK2_FWD, st);
     // NVFI_X6W_UNI: 1 (default) eval renders on the one-wave-per-tile kernel of vel_x6w.hip (bit-identical; an 800 x 800 test frame 134 -> 120 ms),
     // 2 training renders too (same stash and records; no faster there: 0.35 against 0.37 ms, the stash stores are not hidden), 0 neither
     const int wuni = sw(NVFI_X6W_UNI);
     if ((wuni >= 1 && !stash) || wuni >= 2) return launch_rk2_x6w_uni(a, cap_samples, stash, st);
-    // (round 6: the two-tiles-per-workgroup variants - NVFI_X6_NT=2 - are retired: never a default, 8 % slower)
-    if (stash && a.r.z_x4) hipLaunchKernelGGL((k_rk2_x6_uni<1, true, true>), dim3((unsigned)tiles), dim3(WG_THREADS), x6_lds_nt1(), st, a);
-    else if (stash) hipLaunchKernelGGL((k_rk2_x6_uni<1, true>), dim3((unsigned)tiles), dim3(WG_THREADS), x6_lds_nt1(), st, a);
-    else hipLaunchKernelGGL((k_rk2_x6_uni<1, false>), dim3((unsigned)tiles), dim3(WG_THREADS), x6_lds_nt1(), st, a);
+    if (stash && a.r.z_x4) hipLaunchKernelGGL((k_rk2_x6_uni<1, true, true>), dim3((unsigned)tiles), dim3(WG_THREADS), X6_LDS_BYTES(1), st, a);
+    else if (stash) hipLaunchKernelGGL((k_rk2_x6_uni<1, true>), dim3((unsigned)tiles), dim3(WG_THREADS), X6_LDS_BYTES(1), st, a);
+    else hipLaunchKernelGGL((k_rk2_x6_uni<1, false>), dim3((unsigned)tiles), dim3(WG_THREADS), X6_LDS_BYTES(1), st, a);
     LAUNCHCK();
     return 0;
 }
@@ -470,7 +419,7 @@ int launch_rk2_x6(const X6Args& a, int64_t cap_points, hipStream_t st) {
     const int64_t tiles = (cap_points + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
     static DeviceOnce once;
-    if (once.lds(X6_ONE_WG_LDS, k_rk2_x6<1>)) return 1;
+    if (once.lds(X6_LDS_BYTES(1), k_rk2_x6<1>)) return 1;
     // default since round 5 (late): one wave per tile, the epilogue in the MFMAs' VALU slots (vel_x6w.hip; bit-identical results, the bench
     // prefilter 0.89 -> 0.83 ms).  NVFI_X6W=0: the four-waves-per-tile kernel below
     // round 6: a SMALL call is latency-bound - its evaluations are a serial chain per tile, 60 k cycles each on one wave (x6w) against ~17.5 k with
@@ -479,7 +428,7 @@ int launch_rk2_x6(const X6Args& a, int64_t cap_points, hipStream_t st) {
     // to 20 evaluations): 1024 tiles (the strong-scaling shard) 0.41 -> 0.19 ms, 4096 tiles 0.45 -> 0.44 ms, 8192 tiles (the full batch) one wave per
     // tile wins (0.80 against 0.89 ms).  train_segm's integrate_pos (3 000-30 000 occupied points, 40-60 evaluations deep): 1.03 -> 0.46 ms.
     if (sw(NVFI_X6W) && tiles > sw(NVFI_X6W_MIN_TILES)) return launch_rk2_x6w(a, cap_points, st);
-    hipLaunchKernelGGL(k_rk2_x6<1>, dim3((unsigned)tiles), dim3(WG_THREADS), x6_lds_nt1(), st, a);
+    hipLaunchKernelGGL(k_rk2_x6<1>, dim3((unsigned)tiles), dim3(WG_THREADS), X6_LDS_BYTES(1), st, a);
     LAUNCHCK();
     return 0;
 }

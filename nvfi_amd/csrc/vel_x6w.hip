@@ -194,7 +194,7 @@ __device__ __forceinline__ void x6w_load_in(const X6W& c, b8_t (&in)[8][3], int 
     in[s][0] = c.ob[((size_t)s * 3 + 0) * 64]; in[s][1] = c.ob[((size_t)s * 3 + 1) * 64]; in[s][2] = c.ob[((size_t)s * 3 + 2) * 64];
 }
 
-// MFMA j (0..5) of K step s: x6_step's order; the first K step of a row tile starts a1 from the constant 0 (a0 holds the bias)
+// MFMA j (0..5) of K step s: x6_mm6's order; the first K step of a row tile starts a1 from the constant 0 (a0 holds the bias)
 template <int J, bool FIRST>
 __device__ __forceinline__ void x6w_mfma(const b8_t& A1, const b8_t& A2, const b8_t& A3, const b8_t (&B)[3], f32x16& a0, f32x16& a1) {
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -437,8 +437,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_rk2_x6w(X6Args a) {
 #pragma unroll 1
     for (int s = 0; s < a.max_steps; ++s) {
         const bool live = active && fabsf(off) > 0.f;
-        const float mm = fminf(fabsf(off), a.dt_max);
-        const float dt = off > 0.f ? mm : (off < 0.f ? -mm : 0.f);
+        const float dt = rk2_point_dt(off, a.dt_max);
         if (!__any(live)) break;
         const float hdt = 0.5f * dt;
         float px = x, py = y, pz = z;

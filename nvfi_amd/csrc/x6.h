@@ -27,8 +27,12 @@ __device__ __forceinline__ void split3(float x, __bf16& t1, __bf16& t2, __bf16& 
     t2 = (__bf16)r1;
     t3 = (__bf16)(r1 - (float)t2);
 }
-// three-term TRUNCATION split of 8 activations -> the B operands of one K step (vel_x6.hip: split3_8, which documents it): t1 = the upper
-// 16 bits of x, r = x - t1 (exact), t2 = the upper 16 bits of r, t3 = r - t2 (<= 8 significant bits); x = t1 + t2 + t3 exactly
+// three-term split of 8 activations -> the B operands of one K step, by TRUNCATION: t1 = the upper 16 bits of x, r = x - t1 (<= 16 significant
+// bits, exact), t2 = the upper 16 bits of r, t3 = r - t2 (<= 8 significant bits: its upper 16 bits ARE the value) - x = t1 + t2 + t3 exactly, like
+// the rounded split the weights get at pack time (split3), for 3 v_perm_b32 + 4 v_and_b32 + 4 v_sub_f32 per PAIR of values instead of 6
+// conversions, 4 shifts / masks and 4 subtractions: the epilogue is VALU time the matrix pipe waits for.  The terms are up to twice as large as
+// rounded ones (|t2| < 2^-7 |x|, |t3| < 2^-15 |x|), so the three dropped term products (w2 x3, w3 x2, w3 x3: < 2^-22 of the product) are too; the
+// error against float64 stays at the fp32 kernels' (tests/test_gpu_x6.py)
 __device__ __forceinline__ void x6_split8(const float* v, b8_t& b1, b8_t& b2, b8_t& b3) {
     unsigned p1[4], p2[4], p3[4];
 #pragma unroll
@@ -46,7 +50,9 @@ __device__ __forceinline__ void x6_split8(const float* v, b8_t& b1, b8_t& b2, b8
     const x6_u32x4 q1 = {p1[0], p1[1], p1[2], p1[3]}, q2 = {p2[0], p2[1], p2[2], p2[3]}, q3 = {p3[0], p3[1], p3[2], p3[3]};
     b1 = __builtin_bit_cast(b8_t, q1); b2 = __builtin_bit_cast(b8_t, q2); b3 = __builtin_bit_cast(b8_t, q3);
 }
-// the six term products of one K step (vel_x6.hip: x6_step): a0 += A1 B1 | a1 += A1 B2 + A2 B2 + A2 B1 + A1 B3 + A3 B1
+// the six term products of one K step for one tile: a0 += A1 B1 (the leading terms: the sum the fp32 MFMA forms, in the same order) ;
+// a1 += A1 B2 + A2 B2 + A2 B1 + A1 B3 + A3 B1 (everything <= 2^-8 of it: rounding among these is 2^-32 of the result).  Two accumulators since
+// round 5 late (three before: a separate one for the 2^-16 class bought nothing measurable and cost 16 registers and 16 adds per drain)
 __device__ __forceinline__ void x6_mm6(const b8_t& A1, const b8_t& A2, const b8_t& A3, const b8_t& B1, const b8_t& B2, const b8_t& B3,
                                        f32x16& a0, f32x16& a1) {
     a0 = MFMA16B(A1, B1, a0);

@@ -245,7 +245,8 @@ def test_ray_lazy_buffers_follow_the_module_and_camera_attributes_are_assignable
 
 def test_switch_table_matches_the_integration_guide_and_is_the_only_reader():
     """csrc/switches.h is the one table of the environment variables the library reads: INTEGRATION section 4 shows the same default for every
-    row, abi.hip's reader is the only getenv of csrc/, and the per-device set-up of a launcher goes through common.h's DeviceOnce (text only)."""
+    row, abi.hip's reader is the only getenv of csrc/, the per-device set-up of a launcher goes through common.h's DeviceOnce, and no launcher keeps a retired sweep switch alive as a
+    `static int x = -1` selector or a kernel alive by explicit instantiation (text only)."""
     csrc = os.path.join(ROOT, "nvfi_amd", "csrc")
     rows = re.findall(r"^\s*X\((NVFI_\w+),\s*(INT|WORD),\s*(\w+)\)", open(os.path.join(csrc, "switches.h")).read(), flags=re.M)
     assert len(rows) == 16 and len({name for name, _, _ in rows}) == 16, rows
@@ -268,3 +269,11 @@ def test_switch_table_matches_the_integration_guide_and_is_the_only_reader():
                  for fn, txt in sources.items()}
     old_idiom = {fn: w for fn, w in old_idiom.items() if w}
     assert not old_idiom, old_idiom
+    # retired sweep switches leave nothing behind: no `static int x = -1;` selector in a launcher (the variant it chose would still be
+    # compiled), and no explicit instantiation that keeps a kernel without a launcher in the library
+    selectors = {fn: re.findall(r"static\s+int\s+\w+\s*=\s*-\s*1\s*;", txt) for fn, txt in sources.items()}
+    selectors = {fn: w for fn, w in selectors.items() if w}
+    assert not selectors, selectors
+    kept = {fn: re.findall(r"^\s*template\s+(?!<)[^;{]*\bk_\w+[^;{]*;", txt, flags=re.M) for fn, txt in sources.items()}
+    kept = {fn: w for fn, w in kept.items() if w}
+    assert not kept, kept

@@ -10,10 +10,10 @@ mkdir -p $REPO/gpurun_out
 python $REPO/tools/rocpd_stats.py $DB $REPO/gpurun_out/dropin_kernel_stats.csv > /dev/null
 python $REPO/tools/step_gaps.py $DB | head -40
 python - $DB <<'PY'
-import sqlite3, sys
+import re, sqlite3, sys
 c = sqlite3.connect(sys.argv[1]).cursor()
 rows = c.execute("select name, start, end from kernels order by start").fetchall()
-marks = [r[1] for r in rows if r[0].startswith("void k_rk2_split<")]
+marks = [r[1] for r in rows if re.match(r"(void )?k_rk2_split(<|\(|$)", r[0])]
 lo, hi = marks[-4], marks[-3]
 step = [r for r in rows if lo <= r[1] < hi]
 ours = [r for r in step if "k_" in r[0].split("(")[0] and ("at::" not in r[0])]

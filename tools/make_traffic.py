@@ -8,13 +8,14 @@ import re
 import sys
 
 # kernel-name patterns per profiler class (regular expressions matched against the start of the demangled name with a leading "void "
-# removed; template arguments change from round to round, so they are matched loosely - a class that matches NO kernel of the trace is
-# reported on stderr instead of silently becoming 0)
+# removed; template arguments change from round to round, so they are matched loosely - k_rk2_split and k_rk2_split_bwd had a template list
+# until round 6, in the committed traces, and have none now - a class that matches NO kernel of the trace is reported on stderr instead of
+# silently becoming 0)
 CLASSES = {
     "wgrad": [r"k_wgrad$", r"k_wgrad_ring8$"],
-    "pde_prefilter": [r"k_rk2_fwd<false, false>", r"k_rk2_split<", r"k_rk2_pre16", r"k_rk2_x6<", r"k_rk2_x6w"],
+    "pde_prefilter": [r"k_rk2_fwd<false, false>", r"k_rk2_split(<|\(|$)", r"k_rk2_pre16", r"k_rk2_x6<", r"k_rk2_x6w"],
     "rk2_fwd": [r"k_rk2_fwd<true, true>", r"k_rk2_split_uni<", r"k_rk2_x6_uni<"],
-    "rk2_bwd": [r"k_rk2_bwd", r"k_rk2_split_bwd<", r"k_rk2_fuse_bwd"],
+    "rk2_bwd": [r"k_rk2_bwd", r"k_rk2_split_bwd(<|\(|$)", r"k_rk2_fuse_bwd"],
     "pde_bwd": [r"k_pde_jet_bwd", r"k_pde_tangent_bwd", r"k_pde_value_bwd", r"k_pde_fuse_bwd"],
     "pde_fwd": [r"k_pde_jet6_fwd", r"k_pde_jet_fwd", r"k_pde_value_fwd", r"k_pde_tangent_fwd"],
     "app_fwd": [r"k_app_fwd<true>", r"k_app_feat$"],

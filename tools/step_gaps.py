@@ -1,14 +1,15 @@
 #!/usr/bin/env python
 """Device idle gaps of one steady-state step of a kernel trace (rocpd sqlite), one stream or several: the step is delimited by a kernel
-that runs once per step (default: the PDE prefilter).  usage: step_gaps.py <db> [marker-prefix] [steps-from-end]"""
+that runs once per step (default: the PDE prefilter).  usage: step_gaps.py <db> [marker-regex] [steps-from-end]"""
+import re
 import sqlite3
 import sys
 
 
-def main(path, marker="void k_rk2_split<", back=3):
+def main(path, marker=r"(void )?k_rk2_split(<|\(|$)", back=3):     # a regular expression matched at the start of the kernel name (with a template list: older traces)
     c = sqlite3.connect(path).cursor()
     rows = c.execute("select name, start, end from kernels order by start").fetchall()
-    marks = [r[1] for r in rows if r[0].startswith(marker)]
+    marks = [r[1] for r in rows if re.match(marker, r[0])]
     lo, hi = marks[-back - 1], marks[-back]
     rows = [r for r in rows if lo <= r[1] < hi]
     busy_end = rows[0][1]
