@@ -213,6 +213,28 @@ int nvfi_maskfield_fwd(const nvfi_mask_desc* m, int64_t N, const float* xyz, flo
                        void* workspace, int64_t workspace_bytes, void* stream);
 int nvfi_maskfield_bwd(const nvfi_mask_desc* m, int64_t N, const float* g_mask, const nvfi_mask_grads* grads, int mode,
                        void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- the objective of the MaskField training step (train_segm.py:182-202; utils/seg_loss.py: dynamic_loss with fit_motion_svd_batch,
+ *      smooth_loss, entropy_loss; additions to ABI v5).  pc (N,3) normalised keyframe-0 points, flow (N,3), mask (N,K) the MaskField output,
+ *      2 <= K <= 16; everything fp32.  One workspace size serves both calls. */
+int nvfi_segloss_workspace_bytes(int64_t N, int K, int k, int64_t* bytes);
+/* k nearest points of the SAME cloud for every point (pytorch3d knn_points(pc, pc, K=k) as smooth_loss uses it, seg_loss.py:96-98):
+ * idx (N,k) int32 ascending by (squared distance, index), the point itself (or a duplicate of it with a lower index) in slot 0; a slot whose
+ * SQUARED distance exceeds `radius` - the reference compares squared distances with its radius - and a slot that does not exist (k > N)
+ * holds slot 0's index, d2 (N,k, optional) holds +inf there.  Exact: a cell grid of side >= sqrt(radius), 27 cells per point, no N x N matrix.
+ * rev_start (N+1) / rev_edge (N*k) (optional, together): reverse adjacency - the edges e = n*k + j with idx[e] = p != n, for every p the
+ * ascending run rev_edge[rev_start[p] .. rev_start[p+1]) (entries from rev_start[N] on are not written) - which nvfi_segloss needs for the
+ * smoothness gradient. */
+int nvfi_knn_self(int64_t N, const float* pc, int k, float radius, int32_t* idx, float* d2, int32_t* rev_start, int32_t* rev_edge,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+/* forward and backward of the three losses in one call.  losses4 (device float[4]) receives the UN-weighted dynamic_loss, smooth_loss and
+ * entropy_loss as the reference functions return them and, in [3], w_dynamic*[0] + w_smooth*[1] + w_entropy*[2]; gmask (N,K, optional) receives grad_scale * d(w_dynamic*dynamic + w_smooth*smooth +
+ * w_entropy*entropy)/d mask (accumulate != 0: is added to).  R (K,3,3), t (K,3): the rigid fit per object (detached, as in seg_loss.py:79:
+ * no SVD backward; the identity where the object's S has a NaN), pc_transformed (N,3, optional) = sum_k mask_k (R_k pc + t_k).
+ * pc = flow = NULL leaves the rigid-fit term out (losses4[0] = 0), idx = NULL the smoothness term (losses4[1] = 0); loss_norm is 1 or 2. */
+int nvfi_segloss(int64_t N, int K, const float* pc, const float* flow, const float* mask, int k, const int32_t* idx,
+                 const int32_t* rev_start, const int32_t* rev_edge, int loss_norm, float epsilon, float w_dynamic, float w_smooth,
+                 float w_entropy, float grad_scale, int accumulate, float* gmask, float* losses4, float* R, float* t,
+                 float* pc_transformed, void* workspace, int64_t workspace_bytes, void* stream);
 /* SHRender (models/tensorf_model_utils.py:292-296 with models/sh.py:87-110, degree 2): view (N,3), feat (N,27) -> rgb (N,3) */
 int nvfi_sh_render(int64_t N, const float* view, const float* feat27, float* rgb, void* stream);
 

@@ -63,6 +63,7 @@ EXPORTS = [
     "nvfi_pde_workspace_bytes", "nvfi_pde_loss", "nvfi_pde_loss_ex", "nvfi_pde_loss_split", "nvfi_plane_regs", "nvfi_plane_regs_dev", "nvfi_adam_step", "nvfi_mse", "nvfi_render_mask", "nvfi_render_export_masked", "nvfi_maskfield_workspace_bytes", "nvfi_maskfield_fwd", "nvfi_maskfield_bwd", "nvfi_sh_render", "nvfi_compute_alpha", "nvfi_gen_rays",
     "nvfi_vel_eval", "nvfi_vel_workspace_bytes", "nvfi_integrate_pos", "nvfi_density_at", "nvfi_app_at", "nvfi_render_mlp", "nvfi_app_workspace_bytes", "nvfi_alpha_workspace_bytes",
     "nvfi_comm_unique_id", "nvfi_comm_init", "nvfi_allreduce_grads", "nvfi_comm_destroy", "nvfi_selftest", "nvfi_debug_act", "nvfi_prof_enable", "nvfi_prof_collect", "nvfi_prof_nclasses",
+    "nvfi_segloss_workspace_bytes", "nvfi_knn_self", "nvfi_segloss",
 ]
 
 _LIB = None

@@ -1,7 +1,7 @@
 """Per-iteration point pipeline of the reference's segmentation training (train_segm.py:126-170), on the HIP kernels:
 jittered volume points -> density at t = 0 -> keep occupied points -> advect them to a random time with the velocity field ->
 (points, flow) for the MaskField losses.  The losses themselves (dynamic rigid-fit / kNN smoothness / entropy,
-train_segm.py:172-186) are PyTorch code in the reference and stay PyTorch here (out of scope)."""
+train_segm.py:182-202) are nvfi_amd/utils/seg_loss.py, on the kernels of csrc/segloss.hip."""
 import numpy as np
 import torch
 
