@@ -321,6 +321,22 @@ typedef struct nvfi_draw_desc {
     int64_t P; float aabb[6]; float* points; float* t;
 } nvfi_draw_desc;
 int nvfi_draw_batch(const nvfi_draw_desc* d, void* stream);
+/* ---- evaluation metrics on the GPU (additions to ABI v5; csrc/metrics.hip).  Both calls are asynchronous on `stream`, clear what they need with a
+ *      kernel, never wait for the device, and repeat bit for bit.  nvfi_metrics_workspace_bytes: kind 0 = nvfi_ssim(B, C, H, W), kind 1 =
+ *      nvfi_segm_confusion (B frames, C = K classes; H, W unused).
+ * nvfi_ssim (utils/metrics.py:32-99): 11-tap Gaussian window (window11: HOST pointer to the fp32 1-D window), no padding, per channel; pred / gt
+ *      are fp32 and addressed by ELEMENT strides (image, channel, row, column), so (B,C,H,W) and channel-last (H,W,C) frames are read in place.
+ *      C <= 4, H, W >= 11.  range_mode 0: dynamic range L as given; 1: derived on the device by the reference's rule from max / min of pred over
+ *      the whole call (max > 128 -> 255, min < -0.5 -> min_val -1); 2: the same per image.  out (B,2) fp64: mean of the SSIM map, mean of cs = v1/v2.
+ * nvfi_segm_confusion: mask (B,N,K) fp32, K <= 32; labels (B,N) int32 in [0,G), G <= 32 -> counts (B,G,K) int64 = pixels with label g whose
+ *      argmax_k mask is k (ties: lowest index), conf_sum (B,K) fp64 = sum of mask[n, argmax] over the pixels predicted k, pred_label (B,N) int32
+ *      (optional), bad_labels (B) int32 = number of labels outside [0,G).  That is a DEFERRED check: the call cannot see it without waiting, so
+ *      such a pixel is counted nowhere (never an out-of-range write) and the caller raises when it reads the results (metric_segm.py). */
+int nvfi_metrics_workspace_bytes(int kind, int64_t B, int C, int H, int W, int64_t* bytes);
+int nvfi_ssim(int64_t B, int C, int H, int W, const float* pred, const int64_t* pred_strides4, const float* gt, const int64_t* gt_strides4,
+              const float* window11, float L, int range_mode, double* out_b2, void* workspace, int64_t workspace_bytes, void* stream);
+int nvfi_segm_confusion(int64_t B, int64_t N, int K, int G, const float* mask, const int32_t* labels, int64_t* counts, double* conf_sum,
+                        int32_t* pred_label, int32_t* bad_labels, void* workspace, int64_t workspace_bytes, void* stream);
 /* The hand-rolled primitives the MLP engine uses instead of libm (engine.h: one-exp2/one-rcp sigmoid, Cody-Waite sin/cos), evaluated
  * element-wise so that tests can bound their error against float64: kind 0 sigmoid, 1 sin, 2 cos, 3 SiLU, 4 SiLU', 5 SiLU''. */
 int nvfi_debug_act(int kind, int64_t n, const float* x, float* y, void* stream);

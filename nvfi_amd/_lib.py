@@ -64,6 +64,7 @@ EXPORTS = [
     "nvfi_vel_eval", "nvfi_vel_workspace_bytes", "nvfi_integrate_pos", "nvfi_density_at", "nvfi_app_at", "nvfi_render_mlp", "nvfi_app_workspace_bytes", "nvfi_alpha_workspace_bytes",
     "nvfi_comm_unique_id", "nvfi_comm_init", "nvfi_allreduce_grads", "nvfi_comm_destroy", "nvfi_selftest", "nvfi_debug_act", "nvfi_prof_enable", "nvfi_prof_collect", "nvfi_prof_nclasses",
     "nvfi_segloss_workspace_bytes", "nvfi_knn_self", "nvfi_segloss",
+    "nvfi_metrics_workspace_bytes", "nvfi_ssim", "nvfi_segm_confusion",
 ]
 
 _LIB = None
@@ -84,6 +85,10 @@ def lib():
         L.nvfi_last_error.restype = C.c_char_p
         for name in EXPORTS:
             getattr(L, name)  # raises AttributeError on a missing symbol
+        i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+        L.nvfi_metrics_workspace_bytes.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, i64p]
+        L.nvfi_ssim.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, fp, i64p, fp, i64p, f32p, C.c_float, C.c_int, fp, fp, C.c_int64, fp]
+        L.nvfi_segm_confusion.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, fp, C.c_int64, fp]
         _LIB = L
     return _LIB
 

@@ -46,20 +46,22 @@ def load_model_checkpoint(cfg, ckpt, device):
 
 
 def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, near, far, white_background=True,
-                           savedir=None, update_alpha_mask=True, device=None):
+                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False):
     """Eval driver (train_nvfi.py:395-459 without the dataset / wandb plumbing): optional `updateAlphaMask` at the current grid
     (`:413`), one `Renderer.render(mode='test')` per (pose, time) frame (`:437`), 8-bit PNGs named r_%03d.png (`:449-451`,
     written with PIL - imageio is not a dependency here) and per-frame / mean PSNR against `targets` (H,W,3 in [0,1]).
 
-    Returns {"psnr": [..], "mean_psnr": float, "images": uint8 array (N,H,W,3)}."""
+    Returns {"psnr": [..], "mean_psnr": float, "images": uint8 array (N,H,W,3)}.  with_ssim=True adds "ssim": [..] and "mean_ssim": the SSIM of
+    every frame against its target (utils.metrics.ssim_frames: the kernel reads the (H,W,3) frames in place; the values come to the host once,
+    after the loop)."""
     import numpy as np
     from ..models import Camera
-    from .metrics import mse2psnr
+    from .metrics import mse2psnr, ssim_frames
     device = device or next(nvfi.parameters()).device
     nvfi.eval()
     if update_alpha_mask:
         nvfi.nvfi.updateAlphaMask(nvfi.nvfi.gridSize)
-    imgs, psnrs = [], []
+    imgs, psnrs, ssims = [], [], []
     with torch.no_grad():
         for idx in range(len(poses)):
             pose = torch.as_tensor(poses[idx], dtype=torch.float32, device=device)
@@ -69,6 +71,8 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
             if targets is not None:
                 tgt = torch.as_tensor(targets[idx], dtype=torch.float32, device=device).reshape(H, W, 3)
                 psnrs.append(mse2psnr(float(torch.mean((rgb - tgt) ** 2))))
+                if with_ssim:
+                    ssims.append(ssim_frames(rgb, tgt))
             imgs.append((rgb.clamp(0, 1).cpu().numpy() * 255.0).astype(np.uint8))
     if savedir is not None:
         os.makedirs(savedir, exist_ok=True)
@@ -78,4 +82,57 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
                 Image.fromarray(img).save(os.path.join(savedir, "r_%03d.png" % idx))
         except ImportError:      # no image writer in this environment: keep the raw frames
             np.save(os.path.join(savedir, "frames.npy"), np.stack(imgs))
-    return {"psnr": psnrs, "mean_psnr": (sum(psnrs) / len(psnrs)) if psnrs else None, "images": np.stack(imgs)}
+    out = {"psnr": psnrs, "mean_psnr": (sum(psnrs) / len(psnrs)) if psnrs else None, "images": np.stack(imgs)}
+    if with_ssim:
+        out["ssim"] = torch.cat(ssims).cpu().tolist() if ssims else []
+        out["mean_ssim"] = (sum(out["ssim"]) / len(out["ssim"])) if ssims else None
+    return out
+
+
+def render_segm_evaluation(nvfi, renderer, mask_field, poses, times, gt_segms, H, W, focal, near, far, white_background=True,
+                           savedir=None, ignore_npoint_thresh=0, n_gt=None, device=None, return_maps=False):
+    """The loop of the reference's test_segm_render.py:87-180 on this path: with `mask_field` attached to the field, one
+    `Renderer.render(mode='test', transfer_vel=True)` per (pose, time) frame, whose composited mask map (H,W,K) goes straight into
+    utils.metric_segm.SegmEvaluator together with the frame's ground-truth labels `gt_segms[i]` (H,W; integers in [0, 32), 0 the background):
+    the kernel call is queued behind the frame and nothing waits for the device until the summary brings the per-frame matrices over.
+    `savedir`: r_%03d_segm_vis.png per frame - the predicted labels aligned to the ground truth's object order (point_segm_util.align_insts'
+    rule), as 8-bit grey levels (the reference's colour table is not part of this project).
+
+    Returns SegmEvaluator.summary(): {"AP", "PQ", "F1", "Pre", "Rec", "mIoU", "RI", ...}; return_maps=True adds "segm_maps", the rendered mask
+    maps (device tensors)."""
+    import numpy as np
+    from ..models import Camera
+    from .metric_segm import SegmEvaluator
+    device = device or next(nvfi.parameters()).device
+    field = nvfi.nvfi
+    saved, field.mask_field = field.mask_field, mask_field
+    nvfi.eval()
+    ev, maps = None, []
+    try:
+        with torch.no_grad():
+            for idx in range(len(poses)):
+                pose = torch.as_tensor(poses[idx], dtype=torch.float32, device=device)
+                cam = Camera(pose, H, W, focal, None, near, far)
+                segm_map = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test", transfer_vel=True)[4]
+                segm_map = segm_map.reshape(H, W, -1)
+                if ev is None:
+                    ev = SegmEvaluator(segm_map.shape[-1], n_gt, keep_labels=savedir is not None)
+                ev.update(segm_map, torch.as_tensor(gt_segms[idx], device=device).reshape(H, W))
+                if return_maps:
+                    maps.append(segm_map)
+    finally:
+        field.mask_field = saved
+    out = ev.summary(ignore_npoint_thresh, aligned=savedir is not None)
+    if savedir is not None:
+        os.makedirs(savedir, exist_ok=True)
+        labels = torch.stack(out["aligned"]).cpu().numpy()
+        vis = (labels * (255 // max(int(labels.max()), 1))).astype(np.uint8)
+        try:
+            from PIL import Image
+            for idx, img in enumerate(vis):
+                Image.fromarray(img).save(os.path.join(savedir, "r_%03d_segm_vis.png" % idx))
+        except ImportError:      # no image writer in this environment: keep the raw label maps
+            np.save(os.path.join(savedir, "segm_labels.npy"), labels)
+    if return_maps:
+        out["segm_maps"] = maps
+    return out
