@@ -82,6 +82,7 @@ typedef struct nvfi_grads {
 #define NVFI_WHITE_BG  2  /* rgb += 1-acc  (white_bg or the random-white coin, tensorf_keyframe.py:740) */
 #define NVFI_TRANSFER  4  /* transfer_vel: base time 0 (models/nvfi.py:30) */
 #define NVFI_WANT_MASK 8  /* plan workspace room for nvfi_render_mask (mask_field attached) */
+#define NVFI_WANT_FLOW 32 /* plan workspace room for nvfi_render_flow */
 #define NVFI_BWD_FORK 16  /* nvfi_render_bwd at a keyframe time: the density half of the backward may run on a library-owned side stream beside the
                            * appearance half (joined before the call returns); for callers that drive a single stream */
 
@@ -200,6 +201,23 @@ int nvfi_render_mask(const nvfi_field_desc* f, const nvfi_mask_desc* m, int64_t 
  * nvfi_maskfield_fwd / nvfi_maskfield_bwd: mask_map = sum_j weight_j * MaskField(xyz_j). */
 int nvfi_render_export_masked(const nvfi_field_desc* f, int64_t R, float t, int flags, void* workspace, int64_t workspace_bytes,
                               int64_t cap, float* xyz_out, int64_t* idx_out, void* stream);
+/* ---- velocity, scene-flow and optical-flow maps of an eval-mode render (an addition to ABI v5; csrc/flow.hip; the reference has no counterpart: its
+ *      Renderer's `velocity` output is the mask map).  Call after nvfi_render_fwd with the same f, R, rays, t, flags (NVFI_WANT_FLOW set, no
+ *      NVFI_TRAIN) and workspace.  Over the appearance-masked samples j of ray r (weight w_j > weight_thres), x_j the UN-warped normalised sample
+ *      position at time t, s = aabbSize / 2:
+ *        vel_map[r]  (R,3) = sum_j w_j s * v_g(x_j, t)                 v_g: VelocityAABB[Sur].forward, world units per unit time
+ *        flow_map[r] (R,3) = sum_j w_j s * (Phi(x_j) - x_j)            Phi(x) = integrate_pos(x, t, t + dt): dt > 0 forward in time, dt == 0 exact zeros
+ *        flow2d[r]   (R,2) = sum_j w_j (pi(P'_j) - pi(P_j))            pixels; P = aabb_min + (x + 1) s, pi the inverse of nvfi_gen_rays for the camera
+ *                                                                     (pose3x4, H, W, focal); a sample whose displaced point is closer than 1e-3
+ *                                                                     in front of the camera contributes nothing; skipped when pose3x4 is NULL
+ *      Each output pointer may be NULL.  A ray without masked samples gets zeros.  Ordered sums, no float atomics: repeats bit for bit.  The masked
+ *      count never reaches the host.  Errors (2): workspace planned without NVFI_WANT_FLOW, NVFI_TRAIN, use_vel == 0, vel_fp16 modes 1 / 2, a dt
+ *      that needs more than 64 RK2 steps.  vel_fp16 bit 3 selects the fp32 MFMA integrator as in nvfi_integrate_pos. */
+int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d,
+                     float t, float dt, int flags, const float* weights,
+                     const float* pose3x4 /* or NULL */, int H, int W, float focal,
+                     float* vel_map, float* flow_map, float* flow2d,   /* each optional */
+                     void* workspace, int64_t workspace_bytes, void* stream);
 /* ---- MaskField on free points, forward and backward: the model train_segm.py:126-227 optimises (models/mask_field.py:68-83;
  *      xyz (N,3) -> softmax mask (N,mask_dim)).  mode & NVFI_MASK_TRAIN keeps the activations in `workspace` for nvfi_maskfield_bwd, which
  *      ACCUMULATES d loss / d W_l, b_l (l = point_fc.0..3, mask_fc) from g_mask = d loss / d mask (N,mask_dim); the points carry

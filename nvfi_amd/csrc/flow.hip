@@ -1,0 +1,180 @@
+// flow.hip - velocity, scene-flow and optical-flow maps of an eval-mode render (nvfi_render_flow; the reference has no counterpart: the fifth
+// output of its Renderer is called `velocity` but is the mask map).
+//
+// An inference-only branch of the render built like the mask branch (render.hip: nvfi_render_mask): it runs behind nvfi_render_fwd on the
+// workspace that call filled and walks the appearance-masked list (mlist, off_m, counters) without the masked count ever reaching the host.
+//   k_flow_gather    x_j (the UN-warped normalised sample position, the fp32 arithmetic of k_sample_fill) and t for every masked sample,
+//                    into the compacted arrays xt (the velocity net's input) and xd (the integrator's in-place state), + the per-point times
+//   launch_vel_eval  v_g(x_j, t): the gated VelBasis evaluation behind nvfi_vel_eval, sized by the device-side count
+//   launch_rk2_x6    Phi(x_j) = integrate_pos(x_j, t, t + dt): the per-point integrator behind nvfi_integrate_pos (x6; vel_fp16 bit 3 or
+//   / launch_rk2_fwd NVFI_INTEGRATE_X6=0: the fp32 MFMA kernel), in place on xd, sized by the device-side count
+//   k_flow_final     per-ray ordered sums through off_m with the world scaling and the pinhole projection in the epilogue
+// No MFMA code is instantiated here (the launchers live in vel.hip / vel_x6.hip / vel_x6w.hip), so the unit needs no packed-fp32 fence.
+#include <string.h>
+#include "common.h"
+#include "render.h"
+#include "vel.h"
+#include "x6.h"
+#include "frags.h"
+
+struct FlowArgs {
+    nvfi_field_desc f;
+    int64_t R; int64_t cap;
+    const int* count; const int* inside; const int* off_m; const int* list;
+    const float* o; const float* d; const float* weight;
+    float t, t1;
+    float4* xt; float4* xd; const float4* vg; float* tb;
+    const float* pose; int H, W; float focal;
+    float* vel_map; float* flow_map; float* flow2d;
+};
+
+// one thread per masked sample: dense index n = ray * S + sample -> the position k_sample_fill gave it before the warp moved it
+__global__ __launch_bounds__(256) void k_flow_gather(FlowArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= *a.count || i >= a.cap) return;
+    const nvfi_field_desc& f = a.f;
+    const int n = a.list[i];
+    const int S = f.n_samples;
+    const int64_t r = n / S;
+    const int j = n - (int)(r * S);
+    const float o[3] = {a.o[3 * r], a.o[3 * r + 1], a.o[3 * r + 2]};
+    const float d[3] = {a.d[3 * r], a.d[3 * r + 1], a.d[3 * r + 2]};
+    const float tmin = ray_tmin(f, *a.inside != 0, o, d);
+    const float rng = (float)j + 0.f;           // (eval: no jitter)
+    const float step = f.step_size * rng;
+    const float z = tmin + step;
+    float xn[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) xn[c] = norm_coord(f, c, o[c] + d[c] * z);
+    a.xt[i] = make_float4(xn[0], xn[1], xn[2], a.t);
+    a.xd[i] = make_float4(xn[0], xn[1], xn[2], 0.f);
+    a.tb[i] = a.t; a.tb[a.cap + i] = a.t1;
+}
+
+// pixel offset (u - W/2, v - H/2) of world point P: c = R^T (P - o_cam), u = W/2 + focal c_x / (-c_z), v = H/2 - focal c_y / (-c_z); depth = -c_z
+__device__ __forceinline__ void flow_project(const float* pose, float focal, const float* P, float& du, float& dv, float& depth) {
+    const float q[3] = {P[0] - pose[3], P[1] - pose[7], P[2] - pose[11]};
+    const float cx = pose[0] * q[0] + pose[4] * q[1] + pose[8] * q[2];
+    const float cy = pose[1] * q[0] + pose[5] * q[1] + pose[9] * q[2];
+    const float cz = pose[2] * q[0] + pose[6] * q[1] + pose[10] * q[2];
+    depth = -cz;
+    du = focal * cx / depth; dv = -(focal * cy / depth);
+}
+
+// one wave per ray; lane = (entry slot e of 8, component c of 8): c 0..2 vel_map, 3..5 flow_map, 6..7 flow2d.  A ray's list is tens of entries:
+// eight entries per pass, every lane sums its own entries in list order, then the eight slots are added in a fixed tree - the same bits every call
+__global__ __launch_bounds__(256) void k_flow_final(FlowArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    const nvfi_field_desc& f = a.f;
+    const int b0 = a.off_m[r], b1 = a.off_m[r + 1];
+    const int c = lane & 7, e0 = lane >> 3;
+    const int ax = c < 3 ? c : (c < 6 ? c - 3 : 0);
+    const float half = (f.aabb[3 + ax] - f.aabb[ax]) / 2.f;
+    float pose[12];
+    if (a.pose) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) pose[k] = a.pose[k];
+    }
+    float s = 0.f;
+    for (int i = b0 + e0; i < b1; i += 8) {
+        const float w = a.weight[a.list[i]];
+        const float4 x0 = a.xt[i], x1 = a.xd[i];
+        float val;
+        if (c < 3) {
+            const float4 v = a.vg[i];
+            val = half * (c == 0 ? v.x : (c == 1 ? v.y : v.z));
+        } else if (c < 6) {
+            val = half * (c == 3 ? x1.x - x0.x : (c == 4 ? x1.y - x0.y : x1.z - x0.z));
+        } else if (a.pose) {
+            float P0[3], P1[3];
+            const float q0[3] = {x0.x, x0.y, x0.z}, q1[3] = {x1.x, x1.y, x1.z};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float hk = (f.aabb[3 + k] - f.aabb[k]) / 2.f;
+                P0[k] = f.aabb[k] + (q0[k] + 1.f) * hk; P1[k] = f.aabb[k] + (q1[k] + 1.f) * hk;
+            }
+            float u0, v0, z0, u1, v1, z1;
+            flow_project(pose, a.focal, P0, u0, v0, z0);
+            flow_project(pose, a.focal, P1, u1, v1, z1);
+            val = z1 < 1e-3f ? 0.f : (c == 6 ? u1 - u0 : v1 - v0);
+        } else val = 0.f;
+        s += w * val;
+    }
+    s += __shfl_xor(s, 8); s += __shfl_xor(s, 16); s += __shfl_xor(s, 32);
+    if (lane < 3) { if (a.vel_map) a.vel_map[3 * r + lane] = s; }
+    else if (lane < 6) { if (a.flow_map) a.flow_map[3 * r + lane - 3] = s; }
+    else if (lane < 8) { if (a.flow2d && a.pose) a.flow2d[2 * r + lane - 6] = s; }
+}
+
+extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d, float t, float dt, int flags,
+                                const float* weights, const float* pose3x4, int H, int W, float focal, float* vel_map, float* flow_map,
+                                float* flow2d, void* workspace, int64_t workspace_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (R <= 0) return 0;
+    if (flags & NVFI_TRAIN) return nvfi_fail(2, "nvfi_render_flow is an inference branch: NVFI_TRAIN renders have none");
+    if (!f->use_vel) return nvfi_fail(2, "nvfi_render_flow needs a field with a velocity net (use_vel = 0)");
+    if (!(flags & NVFI_WANT_FLOW)) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
+    const int vf = f->vel_fp16 & 3;
+    if (vf == 1 || vf == 2) return nvfi_fail(2, "nvfi_render_flow has no fp16-input integrator (vel_fp16 = %d): use 0, 3 or bit 3", f->vel_fp16);
+    FlowView V;
+    if (int rc = render_flow_view(f, R, flags, t, workspace, &V)) return rc;
+    if (V.total > workspace_bytes)
+        return nvfi_fail(2, "workspace of %lld bytes, a plan with NVFI_WANT_FLOW needs %lld: nvfi_render_flow needs a workspace planned with the flag", (long long)workspace_bytes, (long long)V.total);
+    if (!V.xt) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
+    const bool want2d = flow2d && pose3x4, want_flow = flow_map || want2d;
+    if (!vel_map && !want_flow) return 0;
+    // the integrator's own recurrence (rk2_point_dt) on the host: a dt that needs more steps than the library's limit is refused, not truncated
+    const float t1 = t + dt, dtm = dt_max_of(*f);
+    {
+        float off = t - t1;
+        int n = 0;
+        while (fabsf(off) > 0.f) {
+            if (n >= MAX_RK_STEPS) return nvfi_fail(2, "dt=%g needs more than %d RK2 steps", dt, MAX_RK_STEPS);
+            const float m = fabsf(off) < dtm ? fabsf(off) : dtm;
+            off = off - (off > 0.f ? m : -m);
+            ++n;
+        }
+    }
+    const int64_t N = V.N;
+    FlowArgs a; memset(&a, 0, sizeof(a));
+    a.f = *f; a.R = R; a.cap = N; a.count = V.count_m; a.inside = V.inside; a.off_m = V.off_m; a.list = V.mlist;
+    a.o = rays_o; a.d = rays_d; a.weight = weights; a.t = t; a.t1 = t1;
+    a.xt = V.xt; a.xd = V.xd; a.vg = V.vg; a.tb = V.tb;
+    a.pose = pose3x4; a.H = H; a.W = W; a.focal = focal;
+    a.vel_map = vel_map; a.flow_map = flow_map; a.flow2d = flow2d;
+    hipLaunchKernelGGL(k_flow_gather, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
+    LAUNCHCK();
+    FragCache FC; const bool cached = f->frags != nullptr;
+    if (cached) frag_cache_layout(f->frags, &FC);
+    const bool x6 = vf == 3 || (sw(NVFI_INTEGRATE_X6) != 0 && !(f->vel_fp16 & 8));
+    VelFrags VW;
+    if (vel_map || (want_flow && !x6)) {
+        PackJobs jobs; jobs.n = 0;
+        if (pack_vel_frags(f->vW, f->vb, cached ? FC.vel : V.vel_frag, &VW, &jobs)) return 3;
+        if (!cached && launch_pack(jobs, st)) return 1;
+    }
+    if (vel_map) {
+        VelEvalArgs va; memset(&va, 0, sizeof(va));
+        va.f = *f; va.Wv = VW; va.N = N; va.count = V.count_m; va.xt = reinterpret_cast<const float*>(V.xt);
+        va.u6 = reinterpret_cast<float*>(V.vg); va.u_stride = 4; va.gated = 1;
+        if (launch_vel_eval(va, st)) return 1;
+    }
+    if (want_flow && t1 != t) {
+        if (x6) {
+            const void* img = cached ? FC.vel_x6 : (const void*)V.x6img;
+            if (!cached && launch_pack_x6(f->vW, V.x6img, st)) return 1;
+            X6Args xa; memset(&xa, 0, sizeof(xa));
+            xa.f = *f; xa.img = img; xa.count = V.count_m; xa.xw = V.xd; xa.pt_t = V.tb; xa.pt_base = V.tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
+            if (launch_rk2_x6(xa, N, st)) return 1;
+        } else {
+            Rk2Args ra; memset(&ra, 0, sizeof(ra));
+            ra.f = *f; ra.Wv = VW; ra.count = V.count_m; ra.xw = V.xd; ra.pt_t = V.tb; ra.pt_base = V.tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
+            if (launch_rk2_fwd(ra, N, false, st)) return 1;
+        }
+    }
+    hipLaunchKernelGGL(k_flow_final, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a);
+    LAUNCHCK();
+    return 0;
+}

@@ -92,6 +92,31 @@ struct ScatterArgs {
     int plane_mask;       // debug: bit p enables scattering into plane p (default 63)
 };
 
+// what nvfi_render_flow (flow.hip) needs of the workspace nvfi_render_fwd filled: the masked list, its per-ray offsets, the device-side counts,
+// and the flow branch's own room (NULL when the workspace was planned without NVFI_WANT_FLOW)
+struct FlowView {
+    int64_t N, total;
+    const int* count_m; const int* inside; const int* off_m; const int* mlist;
+    float* vel_frag; float4 *xt, *xd, *vg; float* tb; float* x6img;
+};
+int render_flow_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, FlowView* V);
+
+#ifdef __HIPCC__
+// first sample depth of a ray (tensorf_base.py:294-300); k_sample / k_sample_fill and the flow branch's position rebuild share it
+__device__ __forceinline__ float ray_tmin(const nvfi_field_desc& f, bool inside, const float* o, const float* d) {
+    if (inside) return f.near_;
+    float m = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float vec = d[c] == 0.f ? 1e-6f : d[c];
+        float ra = (f.aabb[3 + c] - o[c]) / vec;
+        float rb = (f.aabb[c] - o[c]) / vec;
+        m = fmaxf(m, fminf(ra, rb));
+    }
+    return fminf(fmaxf(m, f.near_), f.far_);
+}
+#endif
+
 __global__ void k_counters(const int* c, int nsteps, int64_t* out, const float* sched = nullptr);
 __global__ void k_unpack_rgb(const float4* in, float* out, int64_t N);
 __global__ void k_pack_xyz4(const float* in, float4* out, int64_t N);

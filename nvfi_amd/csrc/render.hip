@@ -31,19 +31,6 @@ __global__ void k_any_inside(nvfi_field_desc f, int64_t R, const float* __restri
     if (__any(hit) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
-__device__ __forceinline__ float ray_tmin(const nvfi_field_desc& f, bool inside, const float* o, const float* d) {
-    if (inside) return f.near_;
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float vec = d[c] == 0.f ? 1e-6f : d[c];
-        float ra = (f.aabb[3 + c] - o[c]) / vec;
-        float rb = (f.aabb[c] - o[c]) / vec;
-        m = fmaxf(m, fminf(ra, rb));
-    }
-    return fminf(fmaxf(m, f.near_), f.far_);
-}
-
 __device__ __forceinline__ float alpha_lookup(const nvfi_field_desc& f, float x, float y, float z) {
     // AlphaGridMask.sample_alpha: trilinear, align_corners=True, zeros padding (tensorf_model_utils.py:433-439)
     const int W = f.am_dims[0], H = f.am_dims[1], D = f.am_dims[2];
@@ -1291,6 +1278,7 @@ struct RenderPlan {
     float *vel_frag, *render_frag, *vel_x4, *vel_x4b; void* img16; void* x6img; void* x6imgT;
     TileWork tw2; float* slabs2;
     float *app_f, *app_b, *zst, *x0st, *rec, *gst, *gg, *maskv, *mask_frag;
+    float4 *flow_xt, *flow_xd, *flow_vg; float *flow_tb, *flow_x6;   // NVFI_WANT_FLOW: the flow branch's room (flow.hip)
     unsigned* app_relu;
     float *slabs;
     long long* shadow;         // NVFI_DETERMINISTIC: int64 fixed-point images of the 12 plane gradients
@@ -1363,7 +1351,27 @@ static void plan_render(const nvfi_field_desc* f, int64_t R, int flags, int nste
             P->rec = B.take<float>((int64_t)nsteps * RK_NF * N);
         }
     }
+    // flow branch (inference, flow.hip): compacted (x, t) of the masked samples, their displaced positions, their gated velocities, the per-point
+    // base times of the integrator and its own x6 image (a keyframe render plans none).  Last, so that the flag moves nothing in front of it
+    P->flow_xt = P->flow_xd = P->flow_vg = nullptr; P->flow_tb = P->flow_x6 = nullptr;
+    if ((flags & NVFI_WANT_FLOW) && !train) {
+        P->flow_xt = B.take<float4>(N); P->flow_xd = B.take<float4>(N); P->flow_vg = B.take<float4>(N);
+        P->flow_tb = B.take<float>(2 * N); P->flow_x6 = B.take<float>(X6_IMAGE_BYTES / 4);
+    }
     P->total = align_up(B.off, 256);
+}
+
+// the parts of the forward's workspace nvfi_render_flow reads and owns (flow.hip)
+int render_flow_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, FlowView* V) {
+    if (check_desc(f)) return 2;
+    float base, dts[MAX_RK_STEPS], tcs[MAX_RK_STEPS];
+    const int nsteps = rk_schedule(f, t, flags, &base, dts, tcs);
+    if (nsteps < 0) return nvfi_fail(2, "t=%g needs more than %d RK2 steps", t, MAX_RK_STEPS);
+    RenderPlan P;
+    plan_render(f, R, flags, nsteps, ws, &P);
+    V->N = P.N; V->total = P.total; V->count_m = P.counters + 1; V->inside = P.counters + 2; V->off_m = P.off_m; V->mlist = P.mlist;
+    V->vel_frag = P.vel_frag; V->xt = P.flow_xt; V->xd = P.flow_xd; V->vg = P.flow_vg; V->tb = P.flow_tb; V->x6img = P.flow_x6;
+    return 0;
 }
 
 extern "C" int nvfi_render_workspace_bytes(const nvfi_field_desc* f, int64_t R, int flags, int64_t* bytes) {

@@ -14,6 +14,8 @@ struct VelEvalArgs {
     const float* xt;   // (N,4)
     float* u6;         // (N,6)
     int gated;
+    const int* count;  // optional device-side count of points (<= N, which then sizes the grid): workgroups beyond it exit at once
+    int u_stride;      // gated only: floats per point in u6, of which the first three are written (0: 6); the ungated (N,6) output has no stride
 };
 
 struct Rk2Args {

@@ -14,16 +14,19 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_vel_eval(VelEvalArgs a) {
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave_id();
     const int64_t i = tile * TILE + (lane & 31);
-    const bool active = i < a.N;
+    const int64_t N = a.count ? (int64_t)*a.count : a.N;
+    if ((int64_t)blockIdx.x * WG_SAMPLES >= N) return;   // workgroup-uniform exit
+    const bool active = i < N;
     float4 q = active ? reinterpret_cast<const float4*>(a.xt)[i] : zero4();
     float o4[4], w[6];
+    const int us = a.u_stride ? a.u_stride : 6;
     velnet_forward<1>(a.Wv, lds_w, lds_b, lane, q, nullptr, nullptr, o4);
     gather6(o4, h, w);
     float v[3];
     vel_from_w(w, q.x, q.y, q.z, v);
     if (a.gated) {
         if (gated_out(a.f, q.x, q.y, q.z)) { v[0] = v[1] = v[2] = 0.f; }
-        if (active && h == 0) { a.u6[6 * i] = v[0]; a.u6[6 * i + 1] = v[1]; a.u6[6 * i + 2] = v[2]; }
+        if (active && h == 0) { a.u6[us * i] = v[0]; a.u6[us * i + 1] = v[1]; a.u6[us * i + 2] = v[2]; }
         return;
     }
     float aw[6], acc3[3];
@@ -108,6 +111,7 @@ int ensure_lds_attrs() {
 }
 
 int launch_vel_eval(const VelEvalArgs& a, hipStream_t st) {
+    if (a.u_stride && (!a.gated || a.u_stride < 3)) return nvfi_fail(2, "launch_vel_eval: u_stride=%d is for the gated (N,3) output only and at least 3", a.u_stride);
     if (ensure_lds_attrs()) return 1;
     int64_t nwg = (a.N + WG_SAMPLES - 1) / WG_SAMPLES;
     if (nwg <= 0) return 0;

@@ -43,6 +43,10 @@ class NVFi(nn.Module):
     def render_ray_transfer(self, t, ray_o, ray_d, white_bg=True, ndc_ray=False):
         return self.nvfi(t, ray_o, ray_d, white_bg, ndc_ray, transfer_vel=True)
 
+    def render_ray_flow(self, t, ray_o, ray_d, dt, camera=None, white_bg=True, transfer_vel=False):
+        """eval-mode render with the velocity, scene-flow and optical-flow maps (TensorVMKeyframeTimeKplane.render_flow)"""
+        return self.nvfi.render_flow(t, ray_o, ray_d, dt, camera=camera, white_bg=white_bg, transfer_vel=transfer_vel)
+
     def update_nvfi_kwargs(self, kwargs):
         """models/nvfi.py:33-35 writes every checkpoint kwarg into the field's __dict__.  Same effect here, except that the two
         entries the C-ABI descriptor caches on the host (aabb, gridSize) go through the buffer / update_stepSize."""

@@ -22,7 +22,7 @@ class Renderer(nn.Module):
         self.eval_chunk = None          # None: derived from the byte budget below; an int pins the internal test-mode chunk (rays)
         self.eval_ws_bytes = _EVAL_WS_BYTES
 
-    def _eval_chunk(self, t, transfer_vel):
+    def _eval_chunk(self, t, transfer_vel, flow=False):
         """Internal chunk of a test-mode frame: the largest multiple of the caller's ray_chunk, at most NVFI_EVAL_CHUNK, whose in-flight
         memory - _EVAL_STREAMS x (nvfi_render_workspace_bytes_t + the (R, S) weights) - stays inside `eval_ws_bytes` (8 GiB by default; the
         workspace and weights grow with nSamples, ~1000 after the last upsampling).  A caller who lowered ray_chunk to bound memory keeps that
@@ -33,13 +33,15 @@ class Renderer(nn.Module):
         field = getattr(self.tensorf, "nvfi", None)
         if field is None or not hasattr(field, "render_workspace_bytes"):
             return base
-        key = (base, int(field.nSamples), self.eval_ws_bytes, bool(transfer_vel), float(t))
+        key = (base, int(field.nSamples), self.eval_ws_bytes, bool(transfer_vel), float(t), bool(flow))
         c = self.__dict__.get("_eval_chunk_cache")
         if c is not None and c[0] == key:
             return c[1]
         chunk = max(base, _EVAL_CHUNK_MAX // base * base)
         while chunk > base:
-            need = _EVAL_STREAMS * (field.render_workspace_bytes(chunk, t, transfer=transfer_vel) + chunk * (int(field.nSamples) + 8) * 4)
+            # (flow: the larger workspace nvfi_render_flow plans, and three more small maps per ray)
+            ws = field.render_workspace_bytes(chunk, t, transfer=transfer_vel, flow=True) if flow else field.render_workspace_bytes(chunk, t, transfer=transfer_vel)
+            need = _EVAL_STREAMS * (ws + chunk * (int(field.nSamples) + (16 if flow else 8)) * 4)
             if need <= self.eval_ws_bytes:
                 break
             chunk = max(base, (chunk // 2) // base * base)
@@ -47,12 +49,27 @@ class Renderer(nn.Module):
         return chunk
 
     def forward(self, t, rays, white_background=False, transfer_vel=False):
+        return self._chunks(t, rays, white_background, transfer_vel, None)
+
+    def render_flow(self, t, rays, dt, camera=None, white_background=False, transfer_vel=False):
+        """Test-mode render of a frame with the velocity field's maps (NVFi.render_ray_flow; the reference has no counterpart) -> rgb, depth,
+        acc, weights, vel_map (..., 3), flow_map (..., 3), flow2d (..., 2) or None without a camera, reshaped to rays.restore_shape.  Same
+        byte-budgeted chunks and side streams as a test-mode `forward`; the chunks are independent, so the result does not depend on them.  A model in training mode is
+        switched to eval mode and stays there, as after `render(mode="test")`: the caller calls `train()` again before the next step."""
+        if self.tensorf.training:
+            self.tensorf.eval()
+        with torch.no_grad():
+            return self._chunks(t, rays, white_background, transfer_vel, (float(dt), camera))
+
+    def _chunks(self, t, rays, white_background, transfer_vel, flow):
         ray_o = rays.ray_origins.reshape(-1, 3)
         ray_d = rays.ray_directions.reshape(-1, 3)
         n_all = ray_o.shape[0]
-        outs = [[], [], [], [], []]
+        outs = [[] for _ in range(5 if flow is None else 7)]
         chunk = self.ray_chunk
-        if ray_o.is_cuda and not torch.is_grad_enabled() and not self.tensorf.training:
+        if flow is not None:
+            chunk = self._eval_chunk(t, transfer_vel, flow=True)
+        elif ray_o.is_cuda and not torch.is_grad_enabled() and not self.tensorf.training:
             # test-mode rays carry no jitter and are independent (tests/test_gpu_edges.py: every prefix of a render equals the render), so the
             # reference's ray_chunk - a memory bound for its (R, S, .) torch intermediates - need not be the launch granularity here: a frame
             # goes through in pieces of up to NVFI_EVAL_CHUNK rays (default 32768: 16 MB of weights at 128 samples per ray; bounded by a byte
@@ -60,6 +77,9 @@ class Renderer(nn.Module):
             chunk = self._eval_chunk(t, transfer_vel)
         n_chunks = n_all // chunk + int(n_all % chunk > 0)
         fn = self.tensorf.render_ray_transfer if transfer_vel else self.tensorf.render_ray
+        if flow is not None:
+            def fn(t_, r_o, r_d, white_bg, ndc):
+                return self.tensorf.render_ray_flow(t_, r_o, r_d, flow[0], camera=flow[1], white_bg=white_bg, transfer_vel=transfer_vel)
         # a test-mode frame is some hundred independent chunks: issued alternately on two side streams, one chunk's velocity warp (matrix pipe)
         # runs beside the other's plane gathers (HBM) - every chunk call owns its workspace and outputs, nothing is shared but the weights.
         # NVFI_EVAL_STREAMS=1: the reference's plain loop on the current stream
@@ -88,8 +108,13 @@ class Renderer(nn.Module):
             for s_ in side:
                 main.wait_stream(s_)
         # (one chunk - every training batch - needs no concatenation: five copy launches less per render)
-        rgb_map, depth_map, acc_map, weights, extra = [o[0] if len(o) == 1 else torch.cat(o, 0) for o in outs]
         shp = tuple(rays.restore_shape)
+        if flow is not None:
+            res = [None if o[0] is None else (o[0] if len(o) == 1 else torch.cat(o, 0)) for o in outs]
+            rgb_map, depth_map, acc_map, weights = res[:4]
+            return (rgb_map.reshape(*shp, 3), depth_map.reshape(*shp), acc_map.reshape(*shp), weights.reshape(*shp, -1),
+                    res[4].reshape(*shp, 3), res[5].reshape(*shp, 3), None if res[6] is None else res[6].reshape(*shp, 2))
+        rgb_map, depth_map, acc_map, weights, extra = [o[0] if len(o) == 1 else torch.cat(o, 0) for o in outs]
         return (rgb_map.reshape(*shp, 3), depth_map.reshape(*shp), acc_map.reshape(*shp),
                 weights.reshape(*shp, -1), extra.reshape(*shp, extra.shape[-1]))
 

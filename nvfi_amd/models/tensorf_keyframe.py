@@ -696,11 +696,12 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             fc["waited"].add(cur.cuda_stream)
         return fc["buf"].data_ptr()
 
-    def render_workspace_bytes(self, R, t, train=False, transfer=False):
-        """bytes nvfi_render_fwd[_t] plans for R rays at time t (include/nvfi_hip.h: nvfi_render_workspace_bytes_t)"""
+    def render_workspace_bytes(self, R, t, train=False, transfer=False, flow=False):
+        """bytes nvfi_render_fwd[_t] plans for R rays at time t (include/nvfi_hip.h: nvfi_render_workspace_bytes_t); flow: with the room
+        nvfi_render_flow needs (render_flow)"""
         nb = C.c_int64(0)
         desc = self._desc()
-        flags = (_lib.NVFI_TRAIN if train else 0) | (_lib.NVFI_TRANSFER if transfer else 0)
+        flags = (_lib.NVFI_TRAIN if train else 0) | (_lib.NVFI_TRANSFER if transfer else 0) | (_lib.NVFI_WANT_FLOW if flow else 0)
         _lib.check(_lib.lib().nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(int(R)), C.c_int(flags), C.c_float(float(t)), C.byref(nb)))
         return int(nb.value)
 
@@ -934,6 +935,56 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         else:
             mask_map = self._mask_map(t, flags, R, weights)
         return rgb, depth, acc, weights, mask_map
+
+    @torch.no_grad()
+    def render_flow(self, t, ray_o, ray_d, dt, camera=None, white_bg=True, transfer_vel=False):
+        """Eval-mode render of one chunk of rays with the velocity field's maps (include/nvfi_hip.h: nvfi_render_flow; the reference has no
+        counterpart) -> rgb, depth, acc, weights, vel_map (R,3), flow_map (R,3), flow2d (R,2) or None.
+
+        Over the appearance-masked samples of a ray (weight > rayMarch_weight_thres, un-warped positions x_j at time t): vel_map = sum_j w_j *
+        aabbSize/2 * v(x_j, t) in world units per unit time; flow_map = sum_j w_j * aabbSize/2 * (integrate_pos(x_j, t, t + dt) - x_j), the 3-D
+        displacement over dt (dt > 0: forward in time; dt == 0: zeros); flow2d = the same displacement projected by `camera` (anything with
+        pose / height / width / focal as models.Camera has them, or a tuple (pose3x4, H, W, focal)) in pixels, None without a camera.
+        One nvfi_render_fwd plus one nvfi_render_flow on the same workspace: the masked count never reaches the host."""
+        if self.training:
+            raise NotImplementedError("render_flow is an inference branch: call .eval() first")
+        if not self.use_vel:
+            raise NotImplementedError("render_flow needs a velocity field (use_vel=False)")
+        if not ray_o.is_cuda or not self.aabb.is_cuda:
+            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
+        L = _lib.lib()
+        ray_o = ray_o.reshape(-1, 3).contiguous().float()
+        ray_d = ray_d.reshape(-1, 3).contiguous().float()
+        R, dev = ray_o.shape[0], ray_o.device
+        flags = _lib.NVFI_WANT_FLOW | (_lib.NVFI_WHITE_BG if white_bg else 0) | (_lib.NVFI_TRANSFER if transfer_vel else 0)
+        t = float(np.float32(float(t)))
+        dt = float(np.float32(float(dt)))
+        pose, H, W, focal = None, 0, 0, 0.0
+        if camera is not None:
+            if isinstance(camera, (tuple, list)):
+                pose, H, W, focal = camera
+            else:
+                pose, H, W, focal = camera.pose, camera.height, camera.width, camera.focal
+            pose = torch.as_tensor(pose, dtype=torch.float32, device=dev)[:3, :4].contiguous()
+        desc = self._desc()
+        S = desc.n_samples
+        nbytes = C.c_int64(0)
+        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        rgb, depth, acc = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
+        weights = torch.empty(R, S, device=dev)
+        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
+        vel_map, flow_map = torch.zeros(R, 3, device=dev), torch.zeros(R, 3, device=dev)
+        flow2d = torch.zeros(R, 2, device=dev) if pose is not None else None
+        if R > 0:
+            _lib.check(L.nvfi_render_fwd(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), None, C.c_float(t), C.c_int(flags),
+                                         _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
+                                         _lib.ptr(counters), _stream_ptr()))
+            _lib.check(L.nvfi_render_flow(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_float(dt), C.c_int(flags),
+                                          _lib.ptr(weights), _lib.ptr(pose), C.c_int(int(H)), C.c_int(int(W)), C.c_float(float(focal)),
+                                          _lib.ptr(vel_map), _lib.ptr(flow_map), _lib.ptr(flow2d), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+            self.last_counters = counters
+        return rgb, depth, acc, weights, vel_map, flow_map, flow2d
 
     def _mask_map_train(self, R, weights):
         """Train-mode mask branch (tensorf_keyframe.py:673-676, 749-753), differentiable like the reference's: the appearance-masked

@@ -46,14 +46,15 @@ def load_model_checkpoint(cfg, ckpt, device):
 
 
 def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, near, far, white_background=True,
-                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False):
+                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False, with_flow=None):
     """Eval driver (train_nvfi.py:395-459 without the dataset / wandb plumbing): optional `updateAlphaMask` at the current grid
     (`:413`), one `Renderer.render(mode='test')` per (pose, time) frame (`:437`), 8-bit PNGs named r_%03d.png (`:449-451`,
     written with PIL - imageio is not a dependency here) and per-frame / mean PSNR against `targets` (H,W,3 in [0,1]).
 
     Returns {"psnr": [..], "mean_psnr": float, "images": uint8 array (N,H,W,3)}.  with_ssim=True adds "ssim": [..] and "mean_ssim": the SSIM of
     every frame against its target (utils.metrics.ssim_frames: the kernel reads the (H,W,3) frames in place; the values come to the host once,
-    after the loop)."""
+    after the loop).  with_flow=dt (default off) renders every frame through Renderer.render_flow instead - same rgb - and adds "flow2d"
+    (N,H,W,2), the optical flow over dt in pixels; with `savedir` its colour coding (utils.flow_vis.flow_to_rgb) is written as r_%03d_flow.png."""
     import numpy as np
     from ..models import Camera
     from .metrics import mse2psnr, ssim_frames
@@ -61,12 +62,17 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     nvfi.eval()
     if update_alpha_mask:
         nvfi.nvfi.updateAlphaMask(nvfi.nvfi.gridSize)
-    imgs, psnrs, ssims = [], [], []
+    imgs, psnrs, ssims, flows = [], [], [], []
     with torch.no_grad():
         for idx in range(len(poses)):
             pose = torch.as_tensor(poses[idx], dtype=torch.float32, device=device)
             cam = Camera(pose, H, W, focal, None, near, far)
-            rgb = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test")[0]
+            if with_flow is None:
+                rgb = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test")[0]
+            else:
+                res = renderer.render_flow(float(times[idx]), cam.rays.to(device), float(with_flow), camera=cam, white_background=white_background)
+                rgb = res[0]
+                flows.append(res[6].reshape(H, W, 2))
             rgb = rgb.reshape(H, W, 3)
             if targets is not None:
                 tgt = torch.as_tensor(targets[idx], dtype=torch.float32, device=device).reshape(H, W, 3)
@@ -80,9 +86,15 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
             from PIL import Image
             for idx, img in enumerate(imgs):
                 Image.fromarray(img).save(os.path.join(savedir, "r_%03d.png" % idx))
+            if flows:
+                from .flow_vis import flow_to_rgb
+                for idx, fl in enumerate(flows):
+                    Image.fromarray((flow_to_rgb(fl).cpu().numpy() * 255.0).astype(np.uint8)).save(os.path.join(savedir, "r_%03d_flow.png" % idx))
         except ImportError:      # no image writer in this environment: keep the raw frames
             np.save(os.path.join(savedir, "frames.npy"), np.stack(imgs))
     out = {"psnr": psnrs, "mean_psnr": (sum(psnrs) / len(psnrs)) if psnrs else None, "images": np.stack(imgs)}
+    if flows:
+        out["flow2d"] = torch.stack(flows).cpu().numpy()
     if with_ssim:
         out["ssim"] = torch.cat(ssims).cpu().tolist() if ssims else []
         out["mean_ssim"] = (sum(out["ssim"]) / len(out["ssim"])) if ssims else None
