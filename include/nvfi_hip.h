@@ -83,6 +83,7 @@ typedef struct nvfi_grads {
 #define NVFI_TRANSFER  4  /* transfer_vel: base time 0 (models/nvfi.py:30) */
 #define NVFI_WANT_MASK 8  /* plan workspace room for nvfi_render_mask (mask_field attached) */
 #define NVFI_WANT_FLOW 32 /* plan workspace room for nvfi_render_flow */
+#define NVFI_WANT_SELECT 64 /* plan workspace room for nvfi_render_fwd_select (one float per sample + the packed MaskField) */
 #define NVFI_BWD_FORK 16  /* nvfi_render_bwd at a keyframe time: the density half of the backward may run on a library-owned side stream beside the
                            * appearance half (joined before the call returns); for callers that drive a single stream */
 
@@ -218,6 +219,34 @@ int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float* rays_o, c
                      const float* pose3x4 /* or NULL */, int H, int W, float focal,
                      float* vel_map, float* flow_map, float* flow2d,   /* each optional */
                      void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- per-object layers and the object-selected render of a MaskField decomposition (additions to ABI v5; csrc/objects.hip; the reference has no
+ *      counterpart).
+ *      nvfi_render_objects: call after nvfi_render_fwd (or nvfi_render_fwd_select) AND nvfi_render_mask with the same f, m, R, t, flags (NVFI_WANT_MASK
+ *      set, no NVFI_TRAIN) and workspace.  M_r the appearance-masked samples of ray r (weight w_j > weight_thres), m_jk the softmax nvfi_render_mask
+ *      stored, c_j the colour the composite used (MLP_PE and SH shading both), z_j the sample depth, k < mask_dim = K:
+ *        obj_acc[r][k]    (R,K)   = sum_{j in M_r} w_j m_jk            the bits of mask_map
+ *        obj_rgb[r][k][:] (R,K,3) = sum_{j in M_r} w_j m_jk c_j        premultiplied: no background, no clamp; sum_k = the colour before background / clamp
+ *        obj_depth[r][k]  (R,K)   = sum_{j in M_r} w_j m_jk z_j        no (1 - acc) far term
+ *      Each output pointer may be NULL.  One pass over a ray's entries gives all 5 K sums; ordered, no float atomics: repeats bit for bit.  A ray
+ *      without masked samples gets exact zeros.  The masked count never reaches the host.  Buffers of the workspace the call relies on: the masked
+ *      list and its per-ray offsets (mlist, off_m: nvfi_render_fwd), the sample depths (xw.w) and the per-sample colours (rgbs) of that call, and
+ *      the per-sample softmax (maskv) nvfi_render_mask wrote.  Whether nvfi_render_mask has run on the workspace cannot be seen from the host
+ *      without a synchronisation: the ORDER fwd -> mask -> objects is the caller's duty (without it maskv is stale or uninitialised).
+ *      Errors (2): NVFI_TRAIN, flags without NVFI_WANT_MASK, a workspace smaller than the plan of these flags.
+ *      nvfi_render_fwd_select: nvfi_render_fwd with, for every valid sample at the warped keyframe position x where its density is looked up,
+ *        s(x) = sum_k select[k] * softmax(MaskField(x))_k,   sigma' = sigma * s(x)
+ *      and everything downstream unchanged on sigma' (alpha, transmittance, weights, the weight > weight_thres appearance mask, appearance, composite,
+ *      depth, acc, background): removing the object in front reveals what is behind it.  select: device float[mask_dim] in [0,1] (1 keeps, 0 removes,
+ *      fractions fade); select == NULL is exactly nvfi_render_fwd (same launches, same bits).  Needs NVFI_WANT_SELECT in flags (the room sits behind
+ *      everything else: the flag moves no other buffer); eval only: NVFI_TRAIN gives error 2.  use_vel == 0 fields are allowed (x is the sample
+ *      position).  Layers of a selected render: nvfi_render_fwd_select -> nvfi_render_mask -> nvfi_render_objects on one workspace. */
+int nvfi_render_objects(const nvfi_field_desc* f, const nvfi_mask_desc* m, int64_t R, float t, int flags, const float* weights,
+                        float* obj_rgb, float* obj_acc, float* obj_depth,   /* each optional */
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int nvfi_render_fwd_select(const nvfi_field_desc* f, const nvfi_mask_desc* m, const float* select /* or NULL */, int64_t R,
+                           const float* rays_o, const float* rays_d, const float* jitter, float t, int flags,
+                           float* rgb, float* depth, float* acc, float* weights,
+                           void* workspace, int64_t workspace_bytes, int64_t* counters, void* stream);
 /* ---- MaskField on free points, forward and backward: the model train_segm.py:126-227 optimises (models/mask_field.py:68-83;
  *      xyz (N,3) -> softmax mask (N,mask_dim)).  mode & NVFI_MASK_TRAIN keeps the activations in `workspace` for nvfi_maskfield_bwd, which
  *      ACCUMULATES d loss / d W_l, b_l (l = point_fc.0..3, mask_fc) from g_mask = d loss / d mask (N,mask_dim); the points carry

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.environ.get("NVFI_LIB", os.path.join(HERE, "csrc", "libnvfi_hip.so"))   # NVFI_LIB: alternative build (experiments)
 fp = C.c_void_p
 
-NVFI_TRAIN, NVFI_WHITE_BG, NVFI_TRANSFER, NVFI_WANT_MASK, NVFI_BWD_FORK, NVFI_WANT_FLOW = 1, 2, 4, 8, 16, 32
+NVFI_TRAIN, NVFI_WHITE_BG, NVFI_TRANSFER, NVFI_WANT_MASK, NVFI_BWD_FORK, NVFI_WANT_FLOW, NVFI_WANT_SELECT = 1, 2, 4, 8, 16, 32, 64
 NCOUNTERS = 8
 
 
@@ -65,7 +65,7 @@ EXPORTS = [
     "nvfi_comm_unique_id", "nvfi_comm_init", "nvfi_allreduce_grads", "nvfi_comm_destroy", "nvfi_selftest", "nvfi_debug_act", "nvfi_prof_enable", "nvfi_prof_collect", "nvfi_prof_nclasses",
     "nvfi_segloss_workspace_bytes", "nvfi_knn_self", "nvfi_segloss",
     "nvfi_metrics_workspace_bytes", "nvfi_ssim", "nvfi_segm_confusion",
-    "nvfi_render_flow",
+    "nvfi_render_flow", "nvfi_render_objects", "nvfi_render_fwd_select",
 ]
 
 _LIB = None
@@ -91,6 +91,8 @@ def lib():
         L.nvfi_ssim.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, fp, i64p, fp, i64p, f32p, C.c_float, C.c_int, fp, fp, C.c_int64, fp]
         L.nvfi_segm_confusion.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, fp, C.c_int64, fp]
         L.nvfi_render_flow.argtypes = [fp, C.c_int64, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
+        L.nvfi_render_objects.argtypes = [fp, fp, C.c_int64, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp]
+        L.nvfi_render_fwd_select.argtypes = [fp, fp, fp, C.c_int64, fp, fp, fp, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp, fp]
         _LIB = L
     return _LIB
 

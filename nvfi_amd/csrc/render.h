@@ -35,6 +35,7 @@ struct WeightArgs {
     const float* xpre; const float4* xw;
     float distance_scale, weight_thres, far_;
     float* weight; uint8_t* mflag; float* acc; float* depth; int* cnt_m;
+    const float* sel;   // nvfi_render_fwd_select: s(x) per dense sample index, written for the valid samples (objects.hip: k_select_fwd); NULL otherwise
     // k_weights_fill (weights + the ordered list of appearance-masked samples in one launch)
     unsigned long long* lb; int* off_m_out; int* mlist; int* total_m;
     // backward
@@ -100,6 +101,17 @@ struct FlowView {
     float* vel_frag; float4 *xt, *xd, *vg; float* tb; float* x6img;
 };
 int render_flow_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, FlowView* V);
+
+// what nvfi_render_objects (objects.hip) reads of the workspace nvfi_render_fwd + nvfi_render_mask filled (maskv NULL: planned without NVFI_WANT_MASK)
+struct ObjView {
+    int64_t N, total;
+    const int* off_m; const int* mlist; const float4* xw; const float4* rgbs; const float* maskv;
+};
+int render_obj_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, ObjView* V);
+// s(x) = sum_k select_k softmax(MaskField(x))_k at the warped keyframe positions of the valid samples, into sel[dense sample index] (objects.hip);
+// frag: room for the packed MaskField fragments (64 K floats), N: the launch capacity, count_v: the device-side valid count
+int launch_select(const nvfi_mask_desc* m, const float* select, const int* count_v, const int* vlist, const float4* xw, float* sel, float* frag,
+                  int64_t N, hipStream_t st);
 
 #ifdef __HIPCC__
 // first sample depth of a ray (tensorf_base.py:294-300); k_sample / k_sample_fill and the flow branch's position rebuild share it

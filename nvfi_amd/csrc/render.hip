@@ -269,6 +269,8 @@ __global__ __launch_bounds__(256) void k_density_bwd(DensityArgs a) {
 
 // ================================================================ volume weights (raw2alpha) + composites
 // one wave per ray; 64-sample segments with a carried transmittance
+// SEL (nvfi_render_fwd_select): sigma' = sigma * s(x).  A sample that is not valid has sigma == 0 exactly (XPRE_INVALID) and no s: it stays 0
+template <bool SEL>
 __global__ __launch_bounds__(256) void k_weights_fwd(WeightArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -283,6 +285,7 @@ __global__ __launch_bounds__(256) void k_weights_fwd(WeightArgs a) {
         float sig = 0.f, dist = 0.f, z = 0.f;
         if (in) {
             sig = softplus_f(a.xpre[n]);
+            if (SEL) sig = sig > 0.f ? sig * a.sel[n] : 0.f;
             z = a.xw[n].w;
             if (j + 1 < S) dist = (a.xw[n + 1].w - z) * a.distance_scale;
         }
@@ -320,6 +323,7 @@ __device__ __forceinline__ void counters_body(const int* c, int nsteps, int64_t*
 
 // k_weights_fwd + the k_fill launch behind it: the ordered list of appearance-masked samples (weight > rayMarch_weight_thres) and the per-ray
 // offsets into it (k_final_fwd / k_weights_bwd read off_m) from the same launch
+template <bool SEL>
 __global__ __launch_bounds__(256) void k_weights_fill(WeightArgs a) {
     __shared__ int cm[4];
     __shared__ unsigned long long excl_sh;
@@ -337,6 +341,7 @@ __global__ __launch_bounds__(256) void k_weights_fill(WeightArgs a) {
             float sig = 0.f, dist = 0.f, z = 0.f;
             if (in) {
                 sig = softplus_f(a.xpre[n]);
+                if (SEL) sig = sig > 0.f ? sig * a.sel[n] : 0.f;
                 z = a.xw[n].w;
                 if (j + 1 < S) dist = (a.xw[n + 1].w - z) * a.distance_scale;
             }
@@ -1279,6 +1284,7 @@ struct RenderPlan {
     TileWork tw2; float* slabs2;
     float *app_f, *app_b, *zst, *x0st, *rec, *gst, *gg, *maskv, *mask_frag;
     float4 *flow_xt, *flow_xd, *flow_vg; float *flow_tb, *flow_x6;   // NVFI_WANT_FLOW: the flow branch's room (flow.hip)
+    float *sel, *sel_frag;     // NVFI_WANT_SELECT: s(x) per dense sample index and the MaskField fragments of nvfi_render_fwd_select (objects.hip)
     unsigned* app_relu;
     float *slabs;
     long long* shadow;         // NVFI_DETERMINISTIC: int64 fixed-point images of the 12 plane gradients
@@ -1358,7 +1364,22 @@ static void plan_render(const nvfi_field_desc* f, int64_t R, int flags, int nste
         P->flow_xt = B.take<float4>(N); P->flow_xd = B.take<float4>(N); P->flow_vg = B.take<float4>(N);
         P->flow_tb = B.take<float>(2 * N); P->flow_x6 = B.take<float>(X6_IMAGE_BYTES / 4);
     }
+    // object-selected render (inference, objects.hip): one float per sample and the packed MaskField.  Behind the flow room: moves nothing either
+    P->sel = P->sel_frag = nullptr;
+    if ((flags & NVFI_WANT_SELECT) && !train) { P->sel = B.take<float>(N); P->sel_frag = B.take<float>(64 * 1024); }
     P->total = align_up(B.off, 256);
+}
+
+// the parts of the forward's workspace nvfi_render_objects reads (objects.hip)
+int render_obj_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, ObjView* V) {
+    if (check_desc(f)) return 2;
+    float base, dts[MAX_RK_STEPS], tcs[MAX_RK_STEPS];
+    const int nsteps = rk_schedule(f, t, flags, &base, dts, tcs);
+    if (nsteps < 0) return nvfi_fail(2, "t=%g needs more than %d RK2 steps", t, MAX_RK_STEPS);
+    RenderPlan P;
+    plan_render(f, R, flags, nsteps, ws, &P);
+    V->N = P.N; V->total = P.total; V->off_m = P.off_m; V->mlist = P.mlist; V->xw = P.xw; V->rgbs = P.rgbs; V->maskv = P.maskv;
+    return 0;
 }
 
 // the parts of the forward's workspace nvfi_render_flow reads and owns (flow.hip)
@@ -1408,7 +1429,19 @@ extern "C" int nvfi_render_fwd(const nvfi_field_desc* f, int64_t R, const float*
 static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d,
                            const float* jitter, float t, const float* t_dev, int flags, float* rgb, float* depth, float* acc,
                            float* weights, void* workspace, int64_t workspace_bytes, int64_t* counters, void* stream,
-                           const float* target, float loss_scale, float* loss, float* g_rgb);
+                           const float* target, float loss_scale, float* loss, float* g_rgb,
+                           const nvfi_mask_desc* sel_m = nullptr, const float* select = nullptr);
+// nvfi_render_fwd with the density of every valid sample scaled by s(x) = sum_k select_k softmax(MaskField(x))_k before the weights (objects.hip)
+extern "C" int nvfi_render_fwd_select(const nvfi_field_desc* f, const nvfi_mask_desc* m, const float* select, int64_t R, const float* rays_o,
+                                      const float* rays_d, const float* jitter, float t, int flags, float* rgb, float* depth, float* acc,
+                                      float* weights, void* workspace, int64_t workspace_bytes, int64_t* counters, void* stream) {
+    if (!select) return nvfi_render_fwd(f, R, rays_o, rays_d, jitter, t, flags, rgb, depth, acc, weights, workspace, workspace_bytes, counters, stream);
+    if (flags & NVFI_TRAIN) return nvfi_fail(2, "nvfi_render_fwd_select is an inference call: NVFI_TRAIN renders have no object selection");
+    if (!(flags & NVFI_WANT_SELECT)) return nvfi_fail(2, "nvfi_render_fwd_select needs a workspace planned with NVFI_WANT_SELECT in flags");
+    if (!m) return nvfi_fail(2, "nvfi_render_fwd_select needs a mask field descriptor");
+    return render_fwd_impl(f, R, rays_o, rays_d, jitter, t, nullptr, flags, rgb, depth, acc, weights, workspace, workspace_bytes, counters, stream,
+                           nullptr, 1.f, nullptr, nullptr, m, select);
+}
 extern "C" int nvfi_render_fwd_t(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d,
                                  const float* jitter, float t, const float* t_dev, int flags, float* rgb, float* depth, float* acc,
                                  float* weights, void* workspace, int64_t workspace_bytes, int64_t* counters, void* stream) {
@@ -1424,7 +1457,7 @@ extern "C" int nvfi_render_fwd_mse(const nvfi_field_desc* f, int64_t R, const fl
 static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d,
                            const float* jitter, float t, const float* t_dev, int flags, float* rgb, float* depth, float* acc,
                            float* weights, void* workspace, int64_t workspace_bytes, int64_t* counters, void* stream,
-                           const float* target, float loss_scale, float* loss, float* g_rgb) {
+                           const float* target, float loss_scale, float* loss, float* g_rgb, const nvfi_mask_desc* sel_m, const float* select) {
     hipStream_t st = (hipStream_t)stream;
     if (check_desc(f)) return 2;
     if (R <= 0) return 0;
@@ -1531,11 +1564,17 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
     WeightArgs wa; memset(&wa, 0, sizeof(wa));
     wa.R = R; wa.S = S; wa.xpre = P.xpre; wa.xw = P.xw; wa.distance_scale = f->distance_scale; wa.weight_thres = f->weight_thres;
     wa.far_ = f->far_; wa.weight = weights; wa.mflag = P.mflag; wa.acc = acc; wa.depth = depth; wa.cnt_m = P.cnt_m;
+    if (select) {   // object selection: the MaskField over the valid list, one float per sample; the weights kernels multiply sigma by it
+        if (launch_select(sel_m, select, P.counters + 0, P.vlist, P.xw, P.sel, P.sel_frag, N, st)) return 1;
+        wa.sel = P.sel;
+    }
     if (fl) {
         wa.lb = P.lb_w; wa.off_m_out = P.off_m; wa.mlist = P.mlist; wa.total_m = P.counters + 1;
-        hipLaunchKernelGGL(k_weights_fill, dim3(ray_blocks), dim3(256), 0, st, wa);
+        if (select) hipLaunchKernelGGL(k_weights_fill<true>, dim3(ray_blocks), dim3(256), 0, st, wa);
+        else hipLaunchKernelGGL(k_weights_fill<false>, dim3(ray_blocks), dim3(256), 0, st, wa);
     } else {
-        hipLaunchKernelGGL(k_weights_fwd, dim3(ray_blocks), dim3(256), 0, st, wa);
+        if (select) hipLaunchKernelGGL(k_weights_fwd<true>, dim3(ray_blocks), dim3(256), 0, st, wa);
+        else hipLaunchKernelGGL(k_weights_fwd<false>, dim3(ray_blocks), dim3(256), 0, st, wa);
         hipLaunchKernelGGL(k_fill, dim3(ray_blocks), dim3(256), 0, st, R, S, P.mflag, P.cnt_m, P.off_m, P.mlist, P.counters + 1);
     }
     LAUNCHCK();

@@ -47,6 +47,10 @@ class NVFi(nn.Module):
         """eval-mode render with the velocity, scene-flow and optical-flow maps (TensorVMKeyframeTimeKplane.render_flow)"""
         return self.nvfi.render_flow(t, ray_o, ray_d, dt, camera=camera, white_bg=white_bg, transfer_vel=transfer_vel)
 
+    def render_ray_objects(self, t, ray_o, ray_d, select=None, white_bg=True, transfer_vel=False):
+        """eval-mode render with the per-object layers of the mask field, optionally object-selected (TensorVMKeyframeTimeKplane.render_objects)"""
+        return self.nvfi.render_objects(t, ray_o, ray_d, select=select, white_bg=white_bg, transfer_vel=transfer_vel)
+
     def update_nvfi_kwargs(self, kwargs):
         """models/nvfi.py:33-35 writes every checkpoint kwarg into the field's __dict__.  Same effect here, except that the two
         entries the C-ABI descriptor caches on the host (aabb, gridSize) go through the buffer / update_stepSize."""

@@ -22,7 +22,7 @@ class Renderer(nn.Module):
         self.eval_chunk = None          # None: derived from the byte budget below; an int pins the internal test-mode chunk (rays)
         self.eval_ws_bytes = _EVAL_WS_BYTES
 
-    def _eval_chunk(self, t, transfer_vel, flow=False):
+    def _eval_chunk(self, t, transfer_vel, flow=False, objects=False):
         """Internal chunk of a test-mode frame: the largest multiple of the caller's ray_chunk, at most NVFI_EVAL_CHUNK, whose in-flight
         memory - _EVAL_STREAMS x (nvfi_render_workspace_bytes_t + the (R, S) weights) - stays inside `eval_ws_bytes` (8 GiB by default; the
         workspace and weights grow with nSamples, ~1000 after the last upsampling).  A caller who lowered ray_chunk to bound memory keeps that
@@ -33,7 +33,7 @@ class Renderer(nn.Module):
         field = getattr(self.tensorf, "nvfi", None)
         if field is None or not hasattr(field, "render_workspace_bytes"):
             return base
-        key = (base, int(field.nSamples), self.eval_ws_bytes, bool(transfer_vel), float(t), bool(flow))
+        key = (base, int(field.nSamples), self.eval_ws_bytes, bool(transfer_vel), float(t), bool(flow), bool(objects))
         c = self.__dict__.get("_eval_chunk_cache")
         if c is not None and c[0] == key:
             return c[1]
@@ -42,6 +42,11 @@ class Renderer(nn.Module):
             # (flow: the larger workspace nvfi_render_flow plans, and three more small maps per ray)
             ws = field.render_workspace_bytes(chunk, t, transfer=transfer_vel, flow=True) if flow else field.render_workspace_bytes(chunk, t, transfer=transfer_vel)
             need = _EVAL_STREAMS * (ws + chunk * (int(field.nSamples) + (16 if flow else 8)) * 4)
+            if objects:
+                # (objects: the workspace with the mask branch's and the select pass's room, and 6 K more floats per ray: mask_map + the layers)
+                k = int(getattr(getattr(field, "mask_field", None), "mask_dim", 32))
+                ws = field.render_workspace_bytes(chunk, t, transfer=transfer_vel, objects=True)
+                need = _EVAL_STREAMS * (ws + chunk * (int(field.nSamples) + 8 + 6 * k) * 4)
             if need <= self.eval_ws_bytes:
                 break
             chunk = max(base, (chunk // 2) // base * base)
@@ -61,13 +66,26 @@ class Renderer(nn.Module):
         with torch.no_grad():
             return self._chunks(t, rays, white_background, transfer_vel, (float(dt), camera))
 
-    def _chunks(self, t, rays, white_background, transfer_vel, flow):
+    def render_objects(self, t, rays, select=None, white_background=False, transfer_vel=False):
+        """Test-mode render of a frame with the per-object layers of the field's mask_field (NVFi.render_ray_objects; the reference has no
+        counterpart) -> rgb, depth, acc, weights, mask_map (..., K), obj_rgb (..., K, 3), obj_acc (..., K), obj_depth (..., K), reshaped to
+        rays.restore_shape.  `select` as in TensorVMKeyframeTimeKplane.render_objects: None, K factors in [0, 1], or integer indices of the
+        objects to keep - the scene is re-rendered without the others, occlusion recomputed.  Same byte-budgeted chunks (the new room counted) and
+        side streams as a test-mode `forward`; the chunks are independent.  A model in training mode is switched to eval mode and stays there."""
+        if self.tensorf.training:
+            self.tensorf.eval()
+        with torch.no_grad():
+            return self._chunks(t, rays, white_background, transfer_vel, None, objects=(select,))
+
+    def _chunks(self, t, rays, white_background, transfer_vel, flow, objects=None):
         ray_o = rays.ray_origins.reshape(-1, 3)
         ray_d = rays.ray_directions.reshape(-1, 3)
         n_all = ray_o.shape[0]
-        outs = [[] for _ in range(5 if flow is None else 7)]
+        outs = [[] for _ in range(8 if objects is not None else 5 if flow is None else 7)]
         chunk = self.ray_chunk
-        if flow is not None:
+        if objects is not None:
+            chunk = self._eval_chunk(t, transfer_vel, objects=True)
+        elif flow is not None:
             chunk = self._eval_chunk(t, transfer_vel, flow=True)
         elif ray_o.is_cuda and not torch.is_grad_enabled() and not self.tensorf.training:
             # test-mode rays carry no jitter and are independent (tests/test_gpu_edges.py: every prefix of a render equals the render), so the
@@ -80,6 +98,13 @@ class Renderer(nn.Module):
         if flow is not None:
             def fn(t_, r_o, r_d, white_bg, ndc):
                 return self.tensorf.render_ray_flow(t_, r_o, r_d, flow[0], camera=flow[1], white_bg=white_bg, transfer_vel=transfer_vel)
+        if objects is not None:
+            field = getattr(self.tensorf, "nvfi", None)
+            if objects[0] is not None and getattr(field, "mask_field", None) is not None:
+                objects = (field._select_vector(objects[0], ray_o.device),)     # once per frame, before the side streams fork
+
+            def fn(t_, r_o, r_d, white_bg, ndc):
+                return self.tensorf.render_ray_objects(t_, r_o, r_d, select=objects[0], white_bg=white_bg, transfer_vel=transfer_vel)
         # a test-mode frame is some hundred independent chunks: issued alternately on two side streams, one chunk's velocity warp (matrix pipe)
         # runs beside the other's plane gathers (HBM) - every chunk call owns its workspace and outputs, nothing is shared but the weights.
         # NVFI_EVAL_STREAMS=1: the reference's plain loop on the current stream
@@ -109,6 +134,11 @@ class Renderer(nn.Module):
                 main.wait_stream(s_)
         # (one chunk - every training batch - needs no concatenation: five copy launches less per render)
         shp = tuple(rays.restore_shape)
+        if objects is not None:
+            res = [o[0] if len(o) == 1 else torch.cat(o, 0) for o in outs]
+            k = res[4].shape[-1]
+            return (res[0].reshape(*shp, 3), res[1].reshape(*shp), res[2].reshape(*shp), res[3].reshape(*shp, -1), res[4].reshape(*shp, k),
+                    res[5].reshape(*shp, k, 3), res[6].reshape(*shp, k), res[7].reshape(*shp, k))
         if flow is not None:
             res = [None if o[0] is None else (o[0] if len(o) == 1 else torch.cat(o, 0)) for o in outs]
             rgb_map, depth_map, acc_map, weights = res[:4]

@@ -696,12 +696,14 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             fc["waited"].add(cur.cuda_stream)
         return fc["buf"].data_ptr()
 
-    def render_workspace_bytes(self, R, t, train=False, transfer=False, flow=False):
+    def render_workspace_bytes(self, R, t, train=False, transfer=False, flow=False, objects=False):
         """bytes nvfi_render_fwd[_t] plans for R rays at time t (include/nvfi_hip.h: nvfi_render_workspace_bytes_t); flow: with the room
-        nvfi_render_flow needs (render_flow)"""
+        nvfi_render_flow needs (render_flow); objects: with the mask branch's and nvfi_render_fwd_select's room (render_objects)"""
         nb = C.c_int64(0)
         desc = self._desc()
         flags = (_lib.NVFI_TRAIN if train else 0) | (_lib.NVFI_TRANSFER if transfer else 0) | (_lib.NVFI_WANT_FLOW if flow else 0)
+        if objects:
+            flags |= _lib.NVFI_WANT_MASK | _lib.NVFI_WANT_SELECT
         _lib.check(_lib.lib().nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(int(R)), C.c_int(flags), C.c_float(float(t)), C.byref(nb)))
         return int(nb.value)
 
@@ -985,6 +987,84 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                                           _lib.ptr(vel_map), _lib.ptr(flow_map), _lib.ptr(flow2d), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
             self.last_counters = counters
         return rgb, depth, acc, weights, vel_map, flow_map, flow2d
+
+    def _select_vector(self, select, dev):
+        """`select` of render_objects as a float32 device tensor (K,) in [0, 1], or None.  Floating-point (or bool) entries: one factor per
+        object, length K.  Integer entries: the indices of the objects to keep (everything else is removed)."""
+        if select is None:
+            return None
+        K = self.mask_field.mask_dim
+        if torch.is_tensor(select) and select.is_cuda and select.dtype == torch.float32 and select.numel() == K:
+            return select.reshape(-1).to(dev).contiguous()      # already prepared (Renderer.render_objects): no host round trip per chunk
+        sel = (select.detach().cpu() if torch.is_tensor(select) else torch.as_tensor(np.asarray(select)))
+        if sel.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            idx = sel.reshape(-1).long()
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= K):
+                raise ValueError(f"select: object index outside [0, {K})")
+            out = torch.zeros(K, dtype=torch.float32)
+            out[idx] = 1.0
+            sel = out
+        sel = sel.reshape(-1).to(torch.float32)
+        if sel.numel() != K:
+            raise ValueError(f"select: {sel.numel()} factors for a mask field of {K} objects")
+        if bool((sel < 0).any()) or bool((sel > 1).any()):
+            raise ValueError("select: factors must lie in [0, 1]")
+        return sel.to(dev).contiguous()
+
+    @torch.no_grad()
+    def render_objects(self, t, ray_o, ray_d, select=None, white_bg=True, transfer_vel=False):
+        """Eval-mode render of one chunk of rays with the per-object layers of the attached mask_field (include/nvfi_hip.h: nvfi_render_objects,
+        nvfi_render_fwd_select; the reference has no counterpart) -> rgb, depth, acc, weights, mask_map (R,K), obj_rgb (R,K,3), obj_acc (R,K),
+        obj_depth (R,K).
+
+        Over the appearance-masked samples of a ray, with m_jk the MaskField softmax at the sample's warped keyframe position: obj_acc = sum_j w_j
+        m_jk (= mask_map), obj_rgb = sum_j w_j m_jk c_j (premultiplied: no background, no clamp; summed over k it is the ray's colour before
+        background and clamp), obj_depth = sum_j w_j m_jk z_j.  `select` (None: the plain render) re-renders the scene with objects removed, kept or
+        faded: a length-K sequence / tensor of factors in [0, 1], or a list of INTEGER object indices to keep.  The density of every sample is
+        scaled by sum_k select_k m_k(x) BEFORE the weights, so occlusion is recomputed: removing the object in front reveals what is behind it
+        (utils.objects_vis.composite_layers, the 2-D recombination of finished layers, cannot).  The layers are then those of the selected render."""
+        if self.training:
+            raise NotImplementedError("render_objects is an inference branch: call .eval() first")
+        if self.mask_field is None:
+            raise NotImplementedError("render_objects needs a mask_field attached to the field")
+        if not ray_o.is_cuda or not self.aabb.is_cuda:
+            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
+        L = _lib.lib()
+        ray_o = ray_o.reshape(-1, 3).contiguous().float()
+        ray_d = ray_d.reshape(-1, 3).contiguous().float()
+        R, dev = ray_o.shape[0], ray_o.device
+        mf = self.mask_field
+        K = mf.mask_dim
+        sel = self._select_vector(select, dev)
+        flags = _lib.NVFI_WANT_MASK | (_lib.NVFI_WHITE_BG if white_bg else 0) | (_lib.NVFI_TRANSFER if transfer_vel else 0)
+        if sel is not None:
+            flags |= _lib.NVFI_WANT_SELECT
+        t = float(np.float32(float(t)))
+        md = _lib.MaskDesc()
+        md.n_layer, md.n_dim, md.mask_dim = len(mf.point_fc), mf.point_fc[0].out_features, K
+        for i, lin in enumerate(list(mf.point_fc) + [mf.mask_fc]):
+            md.W[i] = _lib.ptr(lin.weight); md.b[i] = _lib.ptr(lin.bias)
+        desc = self._desc()
+        S = desc.n_samples
+        nbytes = C.c_int64(0)
+        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        rgb, depth, acc = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
+        weights = torch.empty(R, S, device=dev)
+        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
+        mask_map, obj_rgb = torch.zeros(R, K, device=dev), torch.zeros(R, K, 3, device=dev)
+        obj_acc, obj_depth = torch.zeros(R, K, device=dev), torch.zeros(R, K, device=dev)
+        if R > 0:
+            _lib.check(L.nvfi_render_fwd_select(C.byref(desc), C.byref(md), _lib.ptr(sel), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), None,
+                                                C.c_float(t), C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights),
+                                                _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), _stream_ptr()))
+            _lib.check(L.nvfi_render_mask(C.byref(desc), C.byref(md), C.c_int64(R), C.c_float(t), C.c_int(flags), _lib.ptr(weights),
+                                          _lib.ptr(mask_map), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+            _lib.check(L.nvfi_render_objects(C.byref(desc), C.byref(md), C.c_int64(R), C.c_float(t), C.c_int(flags), _lib.ptr(weights),
+                                             _lib.ptr(obj_rgb), _lib.ptr(obj_acc), _lib.ptr(obj_depth), _lib.ptr(ws), C.c_int64(ws.numel()),
+                                             _stream_ptr()))
+            self.last_counters = counters
+        return rgb, depth, acc, weights, mask_map, obj_rgb, obj_acc, obj_depth
 
     def _mask_map_train(self, R, weights):
         """Train-mode mask branch (tensorf_keyframe.py:673-676, 749-753), differentiable like the reference's: the appearance-masked

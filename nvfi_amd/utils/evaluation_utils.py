@@ -101,8 +101,22 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     return out
 
 
+def _save_layers(savedir, idx, obj_rgb, obj_acc):
+    """r_%03d_obj%d.png: one straight-alpha RGBA image per object of frame idx (raw arrays where no image writer is installed)"""
+    import numpy as np
+    from .objects_vis import layer_to_rgba
+    os.makedirs(savedir, exist_ok=True)
+    for k in range(obj_acc.shape[-1]):
+        img = (layer_to_rgba(obj_rgb, obj_acc, k).cpu().numpy() * 255.0).astype(np.uint8)
+        try:
+            from PIL import Image
+            Image.fromarray(img, "RGBA").save(os.path.join(savedir, "r_%03d_obj%d.png" % (idx, k)))
+        except ImportError:
+            np.save(os.path.join(savedir, "r_%03d_obj%d.npy" % (idx, k)), img)
+
+
 def render_segm_evaluation(nvfi, renderer, mask_field, poses, times, gt_segms, H, W, focal, near, far, white_background=True,
-                           savedir=None, ignore_npoint_thresh=0, n_gt=None, device=None, return_maps=False):
+                           savedir=None, ignore_npoint_thresh=0, n_gt=None, device=None, return_maps=False, with_layers=False):
     """The loop of the reference's test_segm_render.py:87-180 on this path: with `mask_field` attached to the field, one
     `Renderer.render(mode='test', transfer_vel=True)` per (pose, time) frame, whose composited mask map (H,W,K) goes straight into
     utils.metric_segm.SegmEvaluator together with the frame's ground-truth labels `gt_segms[i]` (H,W; integers in [0, 32), 0 the background):
@@ -111,7 +125,9 @@ def render_segm_evaluation(nvfi, renderer, mask_field, poses, times, gt_segms, H
     rule), as 8-bit grey levels (the reference's colour table is not part of this project).
 
     Returns SegmEvaluator.summary(): {"AP", "PQ", "F1", "Pre", "Rec", "mIoU", "RI", ...}; return_maps=True adds "segm_maps", the rendered mask
-    maps (device tensors)."""
+    maps (device tensors).  with_layers=True (default off: the function is as before) renders every frame through Renderer.render_objects
+    instead - same mask map - and, with `savedir`, writes each object's layer as a straight-alpha RGBA image r_%03d_obj%d.png
+    (utils.objects_vis.layer_to_rgba)."""
     import numpy as np
     from ..models import Camera
     from .metric_segm import SegmEvaluator
@@ -125,7 +141,13 @@ def render_segm_evaluation(nvfi, renderer, mask_field, poses, times, gt_segms, H
             for idx in range(len(poses)):
                 pose = torch.as_tensor(poses[idx], dtype=torch.float32, device=device)
                 cam = Camera(pose, H, W, focal, None, near, far)
-                segm_map = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test", transfer_vel=True)[4]
+                if with_layers:
+                    res = renderer.render_objects(float(times[idx]), cam.rays.to(device), white_background=white_background, transfer_vel=True)
+                    segm_map = res[4]
+                    if savedir is not None:
+                        _save_layers(savedir, idx, res[5].reshape(H, W, -1, 3), res[6].reshape(H, W, -1))
+                else:
+                    segm_map = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test", transfer_vel=True)[4]
                 segm_map = segm_map.reshape(H, W, -1)
                 if ev is None:
                     ev = SegmEvaluator(segm_map.shape[-1], n_gt, keep_labels=savedir is not None)
