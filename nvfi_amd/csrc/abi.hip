@@ -5,7 +5,7 @@
 #include <string.h>
 #include "common.h"
 #include "pde.h"
-#include "scatter.h"
+#include "render.h"
 #include "vel.h"
 #include "x6.h"
 #include "frags.h"

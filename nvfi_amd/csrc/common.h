@@ -95,13 +95,14 @@ struct Bump {
 // ---------------------------------------------------------------- device-side time schedule
 // A render normally gets its frame time as a host scalar, from which the host derives the keyframe time row (tn), the RK2 step
 // sequence (dt, t) and passes them by value.  For hipGraph replay the same quantities can instead be produced ON THE DEVICE from a
-// time held in device memory (k_sched, render.hip) into a small record in the call's workspace; every kernel argument block carries
+// time held in device memory (k_sched, render_rays.hip) into a small record in the call's workspace; every kernel argument block carries
 // an optional pointer to that record and prefers it over its by-value copy.  Layout (floats):
 //   [0] tn   [1] y0 (int bits: first time row of the LDS scatter variants)   [2] nsteps (int bits)   [3] mismatch flag (int bits)
 //   [8 + s] dt of RK2 step s     [8 + 64 + s] start time of step s
+#define MAX_RK_STEPS 64
 #define SCHED_DT 8
-#define SCHED_TC (8 + 64)
-#define SCHED_FLOATS (8 + 2 * 64)
+#define SCHED_TC (8 + MAX_RK_STEPS)
+#define SCHED_FLOATS (8 + 2 * MAX_RK_STEPS)
 #define SCHED_TN(a) ((a).sched ? (a).sched[0] : (a).tn)
 #define SCHED_Y0(a) ((a).sched ? __float_as_int((a).sched[1]) : (a).y0)
 #define RK_DT(a, s) ((a).sched ? (a).sched[SCHED_DT + (s)] : (a).dt[s])
@@ -137,6 +138,33 @@ __host__ __device__ inline float snap_base(const nvfi_field_desc& f, float t) { 
 __host__ __device__ inline bool is_close(float a, float b) { return fabsf(a - b) <= 1e-8f + fabsf(1e-5f * b); }
 __host__ __device__ inline float dt_max_of(const nvfi_field_desc& f) {
     return f.K > 1 ? (float)(0.5 * (double)f.tmax / (double)(f.K - 1)) : 1.f;
+}
+
+// number of RK2 steps back to the keyframe time and their (dt, start time) sequence for a per-call scalar t (tensorf_keyframe.py:575-609);
+// -1: more than MAX_RK_STEPS.  The ONE copy of the loop: the host plans with it, k_sched / k_prologue (render_rays.hip) replay it on the device
+__host__ __device__ inline int rk_schedule(const nvfi_field_desc& f, float t, int flags, float* base_out, float* dts, float* tcs) {
+    float base = (flags & NVFI_TRANSFER) ? 0.f : snap_base(f, t);
+    *base_out = base;
+    if (!f.use_vel || is_close(t, base)) return 0;
+    float dtm = dt_max_of(f), off = t - base, tc = t;
+    int n = 0;
+    while (fabsf(off) > 0.f) {
+        if (n >= MAX_RK_STEPS) return -1;
+        float m = fabsf(off) < dtm ? fabsf(off) : dtm;
+        float dt = off > 0.f ? m : -m;
+        dts[n] = dt; tcs[n] = tc;
+        off = off - dt; tc = tc - dt;
+        ++n;
+    }
+    return n;
+}
+// first row of the time planes a call at normalised time tn touches (the LDS scatter variants keep rows y0, y0 + 1 in the workgroup), for the host
+// and for sched_body.  bl_setup_xy keeps its own copy of these lines: routed through a shared helper, 13 kernels that call it change instruction order
+__host__ __device__ inline int time_row0(const nvfi_field_desc& f, float tn) {
+    const float y = (tn + 1.f) * ((float)(f.K - 1) / 2.f);
+    float yf = floorf(y);
+    yf = fminf(fmaxf(yf, -4.f), (float)f.K + 2.f);
+    return (int)yf;
 }
 
 __device__ __forceinline__ bool gated_out(const nvfi_field_desc& f, float x, float y, float z) {

@@ -1,7 +1,7 @@
 // flow.hip - velocity, scene-flow and optical-flow maps of an eval-mode render (nvfi_render_flow; the reference has no counterpart: the fifth
 // output of its Renderer is called `velocity` but is the mask map).
 //
-// An inference-only branch of the render built like the mask branch (render.hip: nvfi_render_mask): it runs behind nvfi_render_fwd on the
+// An inference-only branch of the render built like the mask branch (render_blocks.hip: nvfi_render_mask): it runs behind nvfi_render_fwd on the
 // workspace that call filled and walks the appearance-masked list (mlist, off_m, counters) without the masked count ever reaching the host.
 //   k_flow_gather    x_j (the UN-warped normalised sample position, the fp32 arithmetic of k_sample_fill) and t for every masked sample,
 //                    into the compacted arrays xt (the velocity net's input) and xd (the integrator's in-place state), + the per-point times
@@ -118,11 +118,13 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
     if (!(flags & NVFI_WANT_FLOW)) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
     const int vf = f->vel_fp16 & 3;
     if (vf == 1 || vf == 2) return nvfi_fail(2, "nvfi_render_flow has no fp16-input integrator (vel_fp16 = %d): use 0, 3 or bit 3", f->vel_fp16);
-    FlowView V;
-    if (int rc = render_flow_view(f, R, flags, t, workspace, &V)) return rc;
-    if (V.total > workspace_bytes)
-        return nvfi_fail(2, "workspace of %lld bytes, a plan with NVFI_WANT_FLOW needs %lld: nvfi_render_flow needs a workspace planned with the flag", (long long)workspace_bytes, (long long)V.total);
-    if (!V.xt) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
+    RenderPlan P;      // the forward's: the masked list, its per-ray offsets, the device-side counts, and the flow branch's own room
+    const int rc = render_plan_at(f, R, flags, t, workspace, workspace_bytes, &P);
+    if (rc == 4)
+        return nvfi_fail(2, "workspace of %lld bytes, a plan with NVFI_WANT_FLOW needs %lld: nvfi_render_flow needs a workspace planned with the flag", (long long)workspace_bytes, (long long)P.total);
+    if (rc) return rc;
+    const int* const count_m = P.counters + 1;
+    if (!P.flow_xt) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
     const bool want2d = flow2d && pose3x4, want_flow = flow_map || want2d;
     if (!vel_map && !want_flow) return 0;
     // the integrator's own recurrence (rk2_point_dt) on the host: a dt that needs more steps than the library's limit is refused, not truncated
@@ -137,11 +139,11 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
             ++n;
         }
     }
-    const int64_t N = V.N;
+    const int64_t N = P.N;
     FlowArgs a; memset(&a, 0, sizeof(a));
-    a.f = *f; a.R = R; a.cap = N; a.count = V.count_m; a.inside = V.inside; a.off_m = V.off_m; a.list = V.mlist;
+    a.f = *f; a.R = R; a.cap = N; a.count = count_m; a.inside = P.counters + 2; a.off_m = P.off_m; a.list = P.mlist;
     a.o = rays_o; a.d = rays_d; a.weight = weights; a.t = t; a.t1 = t1;
-    a.xt = V.xt; a.xd = V.xd; a.vg = V.vg; a.tb = V.tb;
+    a.xt = P.flow_xt; a.xd = P.flow_xd; a.vg = P.flow_vg; a.tb = P.flow_tb;
     a.pose = pose3x4; a.H = H; a.W = W; a.focal = focal;
     a.vel_map = vel_map; a.flow_map = flow_map; a.flow2d = flow2d;
     hipLaunchKernelGGL(k_flow_gather, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
@@ -152,25 +154,25 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
     VelFrags VW;
     if (vel_map || (want_flow && !x6)) {
         PackJobs jobs; jobs.n = 0;
-        if (pack_vel_frags(f->vW, f->vb, cached ? FC.vel : V.vel_frag, &VW, &jobs)) return 3;
+        if (pack_vel_frags(f->vW, f->vb, cached ? FC.vel : P.vel_frag, &VW, &jobs)) return 3;
         if (!cached && launch_pack(jobs, st)) return 1;
     }
     if (vel_map) {
         VelEvalArgs va; memset(&va, 0, sizeof(va));
-        va.f = *f; va.Wv = VW; va.N = N; va.count = V.count_m; va.xt = reinterpret_cast<const float*>(V.xt);
-        va.u6 = reinterpret_cast<float*>(V.vg); va.u_stride = 4; va.gated = 1;
+        va.f = *f; va.Wv = VW; va.N = N; va.count = count_m; va.xt = reinterpret_cast<const float*>(P.flow_xt);
+        va.u6 = reinterpret_cast<float*>(P.flow_vg); va.u_stride = 4; va.gated = 1;
         if (launch_vel_eval(va, st)) return 1;
     }
     if (want_flow && t1 != t) {
         if (x6) {
-            const void* img = cached ? FC.vel_x6 : (const void*)V.x6img;
-            if (!cached && launch_pack_x6(f->vW, V.x6img, st)) return 1;
+            const void* img = cached ? FC.vel_x6 : (const void*)P.flow_x6;
+            if (!cached && launch_pack_x6(f->vW, P.flow_x6, st)) return 1;
             X6Args xa; memset(&xa, 0, sizeof(xa));
-            xa.f = *f; xa.img = img; xa.count = V.count_m; xa.xw = V.xd; xa.pt_t = V.tb; xa.pt_base = V.tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
+            xa.f = *f; xa.img = img; xa.count = count_m; xa.xw = P.flow_xd; xa.pt_t = P.flow_tb; xa.pt_base = P.flow_tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
             if (launch_rk2_x6(xa, N, st)) return 1;
         } else {
             Rk2Args ra; memset(&ra, 0, sizeof(ra));
-            ra.f = *f; ra.Wv = VW; ra.count = V.count_m; ra.xw = V.xd; ra.pt_t = V.tb; ra.pt_base = V.tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
+            ra.f = *f; ra.Wv = VW; ra.count = count_m; ra.xw = P.flow_xd; ra.pt_t = P.flow_tb; ra.pt_base = P.flow_tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
             if (launch_rk2_fwd(ra, N, false, st)) return 1;
         }
     }

@@ -1,7 +1,7 @@
 // objects.hip - per-object layers and the object-selected render of a MaskField decomposition (nvfi_render_objects, and the hot path of
 // nvfi_render_fwd_select; the reference has no counterpart: its mask branch stops at the soft label map, tensorf_keyframe.py:749-753).
 //
-// Both are inference branches of the render, built like the mask and flow branches (render.hip: nvfi_render_mask, flow.hip):
+// Both are inference branches of the render, built like the mask and flow branches (render_blocks.hip: nvfi_render_mask, flow.hip):
 //   k_obj_final     behind nvfi_render_fwd + nvfi_render_mask on the workspace they filled: one wave per ray walks the ray's appearance-masked
 //                   entries ONCE (off_m, mlist) and accumulates, per object k, sum w m_k, sum w m_k c (3) and sum w m_k z - all 5 K sums of the
 //                   ray from that one pass, in list order, without atomics.  The lane layout (entry parity x 32 channels) and the order of the
@@ -160,14 +160,15 @@ extern "C" int nvfi_render_objects(const nvfi_field_desc* f, const nvfi_mask_des
     if (R <= 0) return 0;
     if (flags & NVFI_TRAIN) return nvfi_fail(2, "nvfi_render_objects is an inference branch: NVFI_TRAIN renders have none");
     if (!(flags & NVFI_WANT_MASK)) return nvfi_fail(2, "nvfi_render_objects needs a workspace planned with NVFI_WANT_MASK in flags");
-    ObjView V;
-    if (int rc = render_obj_view(f, R, flags, t, workspace, &V)) return rc;
-    if (V.total > workspace_bytes)
-        return nvfi_fail(2, "workspace of %lld bytes, the plan of these flags needs %lld: nvfi_render_objects needs the workspace of the render call", (long long)workspace_bytes, (long long)V.total);
-    if (!V.maskv) return nvfi_fail(2, "nvfi_render_objects needs a workspace planned with NVFI_WANT_MASK in flags");
+    RenderPlan P;      // what nvfi_render_fwd + nvfi_render_mask filled
+    const int rc = render_plan_at(f, R, flags, t, workspace, workspace_bytes, &P);
+    if (rc == 4)
+        return nvfi_fail(2, "workspace of %lld bytes, the plan of these flags needs %lld: nvfi_render_objects needs the workspace of the render call", (long long)workspace_bytes, (long long)P.total);
+    if (rc) return rc;
+    if (!P.maskv) return nvfi_fail(2, "nvfi_render_objects needs a workspace planned with NVFI_WANT_MASK in flags");
     if (!obj_rgb && !obj_acc && !obj_depth) return 0;
     ObjArgs a; memset(&a, 0, sizeof(a));
-    a.R = R; a.K = m->mask_dim; a.off_m = V.off_m; a.list = V.mlist; a.weight = weights; a.xw = V.xw; a.rgbs = V.rgbs; a.maskv = V.maskv;
+    a.R = R; a.K = m->mask_dim; a.off_m = P.off_m; a.list = P.mlist; a.weight = weights; a.xw = P.xw; a.rgbs = P.rgbs; a.maskv = P.maskv;
     a.obj_rgb = obj_rgb; a.obj_acc = obj_acc; a.obj_depth = obj_depth;
     hipLaunchKernelGGL(k_obj_final, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a);
     LAUNCHCK();

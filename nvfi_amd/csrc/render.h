@@ -1,8 +1,11 @@
-// render.h - argument blocks of the render kernels (render.hip)
+// render.h - the render step's internal header: argument blocks of its kernels, the workspace plan, and the launchers of its units -
+// render_rays.hip (per-ray stages), render_app.hip (appearance MLP), render.hip (plan, forward, backward), render_blocks.hip (stand-alone
+// calls and the inference mask branch); the plane-gradient scatters are scatter.h's
 #pragma once
 #include <string.h>
 #include "common.h"
 #include "vel.h"
+#include "scatter.h"
 
 struct SampleArgs {
     nvfi_field_desc f;
@@ -81,33 +84,41 @@ struct AppArgs {
     int plane_tail;      // 1: coordinate gradients of the plane lookups (+ in-kernel scatter when gg is NULL) are computed here; 0: k_og does it (or nobody needs them)
 };
 
-struct ScatterArgs {
-    nvfi_field_desc f;
-    const int* count; const int* list;
-    const float4* xw; float tn;
-    const float* sched;
-    const float* gxpre;   // density: one upstream gradient per sample
-    const float* gg;      // appearance: (M,48)
-    nvfi_grads g;
-    int y0, gmax;         // LDS variant: first time row touched by this call, max grid extent
-    int plane_mask;       // debug: bit p enables scattering into plane p (default 63)
+// device-side schedule (k_sched / k_prologue): the field, the device time (NULL: the host's t holds) and the host's plan to fall back to
+struct SchedArgs {
+    nvfi_field_desc f; const float* t_dev; int flags; int nsteps_plan; float tn_plan; float dt_plan[4]; float tc_plan[4]; float* sched;
 };
 
-// what nvfi_render_flow (flow.hip) needs of the workspace nvfi_render_fwd filled: the masked list, its per-ray offsets, the device-side counts,
-// and the flow branch's own room (NULL when the workspace was planned without NVFI_WANT_FLOW)
-struct FlowView {
-    int64_t N, total;
-    const int* count_m; const int* inside; const int* off_m; const int* mlist;
-    float* vel_frag; float4 *xt, *xd, *vg; float* tb; float* x6img;
+// the workspace of a render call.  nvfi_render_fwd fills it; the backward and the inference branches behind the forward (mask, flow,
+// objects, export) plan the same call again and read it
+struct RenderPlan {
+    int64_t N, cap_tiles;
+    int nsteps;
+    float* sched;       // device-side schedule record (SCHED_FLOATS), written by k_sched when the call passes a device time
+    int* counters;      // [0] V, [1] M, [2] inside flag
+    int *cnt_v, *off_v, *cnt_m, *off_m, *vlist, *mlist, *cnt_r, *off_r, *rlist;
+    uint8_t *valid, *mflag, *rflag;
+    float4 *xw, *rgbs, *rgb_pre, *gxw, *gxk;
+    float *xpre, *gxpre;
+    float *vel_frag, *render_frag, *vel_x4, *vel_x4b; void* img16; void* x6img; void* x6imgT;
+    TileWork tw2; float* slabs2;
+    float *app_f, *app_b, *zst, *x0st, *rec, *gst, *gg, *maskv, *mask_frag;
+    float4 *flow_xt, *flow_xd, *flow_vg; float *flow_tb, *flow_x6;   // NVFI_WANT_FLOW: the flow branch's room (flow.hip)
+    float *sel, *sel_frag;     // NVFI_WANT_SELECT: s(x) per dense sample index and the MaskField fragments of nvfi_render_fwd_select (objects.hip)
+    unsigned* app_relu;
+    float *slabs;
+    long long* shadow;         // NVFI_DETERMINISTIC: int64 fixed-point images of the 12 plane gradients
+    int64_t zero_bytes;        // counters .. end of the sort histograms / look-back words: zeroed by the forward's single fill (or k_prologue)
+    unsigned long long *lb_s, *lb_w;   // look-back status words of k_sample_fill / k_weights_fill
+    float* mse_part;
+    TileWork tw; bool tiles;   // sorted-tile plane scatter (scatter.hip); tiles = false: grid too large, atomic scatter instead
+    int64_t total;
 };
-int render_flow_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, FlowView* V);
-
-// what nvfi_render_objects (objects.hip) reads of the workspace nvfi_render_fwd + nvfi_render_mask filled (maskv NULL: planned without NVFI_WANT_MASK)
-struct ObjView {
-    int64_t N, total;
-    const int* off_m; const int* mlist; const float4* xw; const float4* rgbs; const float* maskv;
-};
-int render_obj_view(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, ObjView* V);
+// THE way to a RenderPlan: descriptor check, RK2 schedule of t (refused beyond MAX_RK_STEPS), plan, and - unless ws is NULL, the
+// *_workspace_bytes calls - the size check (code 4; P->total is set).  base / dts / tcs: the schedule for callers that want it, or NULL
+int check_desc(const nvfi_field_desc* f);
+int render_plan_at(const nvfi_field_desc* f, int64_t R, int flags, float t, void* ws, int64_t ws_bytes, RenderPlan* P, float* base = nullptr,
+                   float* dts = nullptr, float* tcs = nullptr);
 // s(x) = sum_k select_k softmax(MaskField(x))_k at the warped keyframe positions of the valid samples, into sel[dense sample index] (objects.hip);
 // frag: room for the packed MaskField fragments (64 K floats), N: the launch capacity, count_v: the device-side valid count
 int launch_select(const nvfi_mask_desc* m, const float* select, const int* count_v, const int* vlist, const float4* xw, float* sel, float* frag,
@@ -129,9 +140,17 @@ __device__ __forceinline__ float ray_tmin(const nvfi_field_desc& f, bool inside,
 }
 #endif
 
-__global__ void k_counters(const int* c, int nsteps, int64_t* out, const float* sched = nullptr);
-__global__ void k_unpack_rgb(const float4* in, float* out, int64_t N);
-__global__ void k_pack_xyz4(const float* in, float4* out, int64_t N);
+// render_rays.hip
+int launch_ray_head(const SchedArgs& sc, int64_t R, const float* rays_o, int* zero_from, int64_t zero_bytes, int* inside, bool fused, hipStream_t st);
+int launch_sample(const SampleArgs& sa, int* off_v, int* off_r, bool fused, hipStream_t st);
+int launch_weights_fwd(const WeightArgs& wa, bool fused, hipStream_t st);
+int launch_final_fwd(FinalArgs fa, int64_t* counters, bool fused, hipStream_t st);
+int launch_weights_bwd(const WeightArgs& wa, hipStream_t st);
+int launch_density_bwd(const DensityArgs& da, int64_t N, hipStream_t st);
+// render_app.hip
+int launch_app_fwd(const AppArgs& aa, int64_t cap_samples, bool stash, hipStream_t st);
+int launch_app_bwd(const AppArgs& aa, int64_t cap_samples, hipStream_t st);
+// render.hip
 int launch_vel_wgrad(const float* zst, const float* x0st, const float* gst, const int* count, int cap_tiles, int nrep,
                      int act_mode, float* slabs, int nslab, float* const* gW, float* const* gb, float scale, hipStream_t st, int fused_nslab = 0,
                      const WgradJobs* pre_w = nullptr, const ReduceJobs* pre_r = nullptr);

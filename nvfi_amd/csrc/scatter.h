@@ -1,7 +1,8 @@
-// scatter.h - sorted-tile plane-gradient scatter and the (sample, channel-quad) gather kernels (scatter.hip)
+// scatter.h - sorted-tile plane-gradient scatter and the (sample, channel-quad) gather kernels (scatter.hip); the atomic / LDS
+// plane-gradient scatter of the grids the tiles do not cover and of NVFI_DETERMINISTIC (scatter_atomic.hip)
 #pragma once
 #include "common.h"
-#include "render.h"
+struct DensityArgs;            // render.h (which includes this header)
 
 #define SCATTER_T 8            // tile edge in texels (LDS tile = (T+1)^2 x 24 floats + a 2 x (T+1) x 24 strip of the paired time plane)
 #ifndef SCATTER_CHUNK
@@ -53,6 +54,18 @@ struct TileScatterArgs {
     nvfi_grads g;
 };
 
+struct ScatterArgs {
+    nvfi_field_desc f;
+    const int* count; const int* list;
+    const float4* xw; float tn;
+    const float* sched;
+    const float* gxpre;   // density: one upstream gradient per sample
+    const float* gg;      // appearance: (M,48)
+    nvfi_grads g;
+    int y0, gmax;         // LDS variant: first time row touched by this call, max grid extent
+    int plane_mask;       // debug: bit p enables scattering into plane p (default 63)
+};
+
 int tile_geom(const nvfi_field_desc* f, TileGeom* g);
 void plan_tile_scatter(Bump& B, const nvfi_field_desc* f, int64_t N, TileWork* w);
 int ensure_scatter_attrs();
@@ -62,3 +75,10 @@ int launch_tile_scatter(const nvfi_field_desc* f, const TileWork& w, const int* 
 int launch_tile_sort(const TileWork* const* w, const int* const* count, const int* const* list, int njobs, const float4* xw, int64_t N, hipStream_t st);
 int launch_app_feat(const OgArgs& oa, int64_t N, hipStream_t st);   // oa.og: feat[i][48], the appearance feature of masked sample i (Ca == 48)
 int launch_density_q(const DensityArgs& da, int64_t N, hipStream_t st);   // Cd == 24 only
+// scatter_atomic.hip.  C = 24: density planes from sa.gxpre over the valid list, 48: appearance planes from sa.gg over the masked list
+int launch_scatter(const nvfi_field_desc* f, ScatterArgs& sa, int C, int64_t N, float tn, hipStream_t st);
+// NVFI_DETERMINISTIC: sa.g addresses the int64 shadow planes (plane_elems: their element offsets in the order dps dpt aps apt, and the total);
+// launch_det_finish folds every shadow plane whose gradient is wanted into it
+int launch_scatter_det(ScatterArgs& sa, int C, int64_t N, hipStream_t st);
+int64_t plane_elems(const nvfi_field_desc* f, int64_t* off /* [12] */);
+int launch_det_finish(const nvfi_field_desc* f, const long long* shadow, const nvfi_grads* grads, hipStream_t st);

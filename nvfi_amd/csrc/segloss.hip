@@ -16,7 +16,7 @@
 //                                     (both ends of every kNN edge through the reverse lists: a gather, no float atomics); losses in two stages
 // Every clear is a kernel (launch_zero), nothing waits for the device, every launch is on the caller's stream.
 //
-// In-launch hand-off (the project's ticket pattern, render.hip k_final_fwd): partial sums are agent-scope atomic stores, every storing wave
+// In-launch hand-off (the project's ticket pattern, render_rays.hip k_final_fwd): partial sums are agent-scope atomic stores, every storing wave
 // drains them (s_waitcnt vmcnt(0)) before the workgroup's barrier, one lane then draws the ticket; the last workgroup reads the partials with
 // agent-scope atomic loads, in workgroup order, so the value does not depend on which workgroup came last.  Tickets are zero at launch.
 #include <limits.h>

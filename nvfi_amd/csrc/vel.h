@@ -4,8 +4,6 @@
 
 #define RK_NF 19                       // per (step, sample) record fields: x3 pmid3 w1[6] w2[6] flags
 #define VEL_G_REGS (5 * 64 + 16)       // adjoint stash rows per (eval, tile): gz[5][64] + gw[16]
-#define MAX_RK_STEPS 64
-static_assert(MAX_RK_STEPS == 64, "SCHED_* offsets in common.h assume 64 RK2 steps");
 
 struct VelEvalArgs {
     nvfi_field_desc f;

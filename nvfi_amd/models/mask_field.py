@@ -3,7 +3,7 @@
 Same constructor, attribute names and state_dict keys as the reference.  `forward(point)` runs the HIP kernels of
 nvfi_amd/csrc/mask.hip through the C ABI (nvfi_maskfield_fwd / nvfi_maskfield_bwd, include/nvfi_hip.h) behind a
 torch.autograd.Function, so the reference's training step (train_segm.py:172-198: mask = model(xyz); loss(mask).backward();
-Adam) runs unchanged on it.  Inside a render the same weights are evaluated by k_mask_fwd (mask branch, render.hip).
+Adam) runs unchanged on it.  Inside a render the same weights are evaluated by k_mask_fwd (mask branch, render_blocks.hip).
 There is no CPU path: tensors must live on the GPU.
 """
 import ctypes as C

@@ -1,5 +1,5 @@
 """AlphaGridMask container (reference models/tensorf_model_utils.py:417-442); the lookup itself runs
-inside the sampling kernel (nvfi_amd/csrc/render.hip: alpha_lookup)."""
+inside the sampling kernel (nvfi_amd/csrc/render_rays.hip: alpha_lookup)."""
 import torch
 
 

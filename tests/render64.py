@@ -344,6 +344,6 @@ def relu_margin(field, rays_o, rays_d, t, jitter, app_mask=None, chunk=256, devi
 
 
 def list_order(mask):
-    """(n, 2) indices of a compacted list in the device's order: ray-major, sample-minor (render.hip: k_weights_fill / k_fill write per-ray
+    """(n, 2) indices of a compacted list in the device's order: ray-major, sample-minor (render_rays.hip: k_weights_fill / k_fill write per-ray
     offsets from an exclusive scan over the rays, samples in order within a ray)"""
     return np.argwhere(mask)

@@ -277,3 +277,81 @@ def test_switch_table_matches_the_integration_guide_and_is_the_only_reader():
     kept = {fn: re.findall(r"^\s*template\s+(?!<)[^;{]*\bk_\w+[^;{]*;", txt, flags=re.M) for fn, txt in sources.items()}
     kept = {fn: w for fn, w in kept.items() if w}
     assert not kept, kept
+
+
+def _plan_desc():
+    """nvfi_field_desc with the sizes of golden field A and no pointers: the workspace plan reads sizes only"""
+    from nvfi_amd import _lib
+    f = make_model("A", device="cpu")[0].nvfi
+    d = _lib.FieldDesc()
+    d.G[:] = f._grid_host
+    d.K, d.Cd, d.Ca, d.app_dim = int(f.num_keyframes), int(f.density_n_comp[0]), int(f.app_n_comp[0]), int(f.app_dim)
+    d.n_samples, d.use_vel, d.tmax = int(f.nSamples), 1, float(f.tmax)
+    return d
+
+
+def _plan_bytes(d, R, flags, t=None):
+    """(return code, bytes) of nvfi_render_workspace_bytes (t None) / nvfi_render_workspace_bytes_t"""
+    import ctypes as C
+    from nvfi_amd import _lib
+    nb = C.c_int64(-1)
+    if t is None:
+        rc = _lib.lib().nvfi_render_workspace_bytes(C.byref(d), C.c_int64(R), C.c_int(flags), C.byref(nb))
+    else:
+        rc = _lib.lib().nvfi_render_workspace_bytes_t(C.byref(d), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nb))
+    return rc, nb.value
+
+
+def _plan_cases(d):
+    """name -> (R, flags, t): R in {5, 8192, 8193}, seven flag sets, the t-independent bound and three times - a keyframe time, one half an RK2
+    step off a keyframe, one two steps past the last keyframe (dt_max = half a keyframe interval)"""
+    from nvfi_amd import _lib as L
+    ts = np.float32(d.tmax) / np.float32(d.K - 1)
+    dtm = np.float32(0.5) * ts
+    times = {"any": None, "key": float(ts), "half": float(ts + np.float32(0.5) * dtm), "two": float(np.float32(d.tmax) + np.float32(2) * dtm)}
+    flagsets = {"0": 0, "T": L.NVFI_TRAIN, "TF": L.NVFI_TRAIN | L.NVFI_BWD_FORK, "M": L.NVFI_WANT_MASK, "F": L.NVFI_WANT_FLOW, "S": L.NVFI_WANT_SELECT,
+                "MFS": L.NVFI_WANT_MASK | L.NVFI_WANT_FLOW | L.NVFI_WANT_SELECT}
+    return {f"{R}:{fn}:{tn}": (R, fl, t) for R in (5, 8192, 8193) for fn, fl in flagsets.items() for tn, t in times.items()}
+
+
+# bytes of the plan before render.hip was split into units (the library of the commit before, same calls, default switches)
+PLAN_BYTES = {
+    "5:0:any": 885248, "5:0:key": 885248, "5:0:half": 1600256, "5:0:two": 1600256,
+    "5:T:any": 215480320, "5:T:key": 104312576, "5:T:half": 211329024, "5:T:two": 215480320,
+    "5:TF:any": 215480320, "5:TF:key": 104312576, "5:TF:half": 211329024, "5:TF:two": 215480320,
+    "5:M:any": 1185280, "5:M:key": 1185280, "5:M:half": 1900288, "5:M:two": 1900288,
+    "5:F:any": 1320192, "5:F:key": 1320192, "5:F:half": 2035200, "5:F:two": 2035200,
+    "5:S:any": 1148672, "5:S:key": 1148672, "5:S:half": 1863680, "5:S:two": 1863680,
+    "5:MFS:any": 1883648, "5:MFS:key": 1883648, "5:MFS:half": 2598656, "5:MFS:two": 2598656,
+    "8192:0:any": 23405568, "8192:0:key": 23405568, "8192:0:half": 26600704, "8192:0:two": 26600704,
+    "8192:T:any": 13467959552, "8192:T:key": 2895663104, "8192:T:half": 8234483968, "8192:T:two": 13467959552,
+    "8192:TF:any": 13467959552, "8192:TF:key": 2895663104, "8192:TF:half": 8234483968, "8192:TF:two": 13467959552,
+    "8192:M:any": 85533696, "8192:M:key": 85533696, "8192:M:half": 88728832, "8192:M:two": 88728832,
+    "8192:F:any": 50889728, "8192:F:key": 50889728, "8192:F:half": 54084864, "8192:F:two": 54084864,
+    "8192:S:any": 25601024, "8192:S:key": 25601024, "8192:S:half": 28796160, "8192:S:two": 28796160,
+    "8192:MFS:any": 115213312, "8192:MFS:key": 115213312, "8192:MFS:half": 118408448, "8192:MFS:two": 118408448,
+    "8193:0:any": 23410176, "8193:0:key": 23410176, "8193:0:half": 26606080, "8193:0:two": 26606080,
+    "8193:T:any": 13471280128, "8193:T:key": 2896221184, "8193:T:half": 8236423680, "8193:T:two": 13471280128,
+    "8193:TF:any": 13471280128, "8193:TF:key": 2896221184, "8193:TF:half": 8236423680, "8193:TF:two": 13471280128,
+    "8193:M:any": 85545984, "8193:M:key": 85545984, "8193:M:half": 88741888, "8193:M:two": 88741888,
+    "8193:F:any": 50897920, "8193:F:key": 50897920, "8193:F:half": 54093824, "8193:F:two": 54093824,
+    "8193:S:any": 25605888, "8193:S:key": 25605888, "8193:S:half": 28801792, "8193:S:two": 28801792,
+    "8193:MFS:any": 115229440, "8193:MFS:key": 115229440, "8193:MFS:half": 118425344, "8193:MFS:two": 118425344,
+}
+
+
+def test_render_workspace_layout_is_pinned():
+    """The workspace plan of a render call (plan_render behind render_plan_at, render.hip) is shared by the forward, the backward and the
+    branches that read the forward's workspace, and by callers that size it: its byte counts for golden field A's sizes are literals.  A time
+    that needs more than MAX_RK_STEPS (64) RK2 steps is refused with code 2."""
+    d = _plan_desc()
+    cases = _plan_cases(d)
+    assert len(cases) == 3 * 7 * 4 and set(cases) == set(PLAN_BYTES)
+    got = {k: _plan_bytes(d, *c) for k, c in cases.items()}
+    assert all(rc == 0 for rc, _ in got.values()), {k: v for k, v in got.items() if v[0]}
+    assert {k: v[1] for k, v in got.items()} == PLAN_BYTES
+    dtm = 0.5 * d.tmax / (d.K - 1)
+    rc, _ = _plan_bytes(d, 8, 0, d.tmax + 65.5 * dtm)
+    from nvfi_amd import _lib
+    assert rc == 2 and b"RK2 steps" in _lib.lib().nvfi_last_error()
+    assert _plan_bytes(d, 8, 0, d.tmax + 63.5 * dtm)[0] == 0

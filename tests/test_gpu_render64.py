@@ -1,4 +1,4 @@
-"""The render step on the device (render.hip, scatter.hip, wgrad_ring.hip, engine.*, vel_fuse / vel_split / vel_x6*.hip: the forward, the three
+"""The render step on the device (render.hip, render_rays.hip, render_app.hip, scatter.hip, scatter_atomic.hip, wgrad_ring.hip, engine.*, vel_fuse / vel_split / vel_x6*.hip: the forward, the three
 compacted lists and the whole backward) against its float64 restatement (tests/render64.py, pinned to the reference's goldens by
 tests/test_render64_golden.py), on the device's own appearance mask where the call returns its weight map.
 
@@ -58,7 +58,7 @@ when the last full 32-sample tile of the masked list (appearance branch) or of t
   threshold (the float32 evaluation flips 8).
 The switch settings agree with the defaults to the printed digits.  NVFI_DETERMINISTIC=1 did not at first: its fixed-point scatter (2^50 per unit,
 8.9e-16 of resolution) quantised the bench field's 1e-10 appearance-plane gradients at 2.5e-3 of their peak, over head_nonkey's 1e-4; the scale is
-2^58 now (render.hip, DET_SCALE) and the setting sits at 3.0e-5 / 6.7e-5 like the others.  The file takes about a minute on its own (nine worker
+2^58 now (scatter_atomic.hip, DET_SCALE) and the setting sits at 3.0e-5 / 6.7e-5 like the others.  The file takes about a minute on its own (nine worker
 processes; the float64 references run on the GPU).
 Two mutations that only skip work, each built and run once: k_app_bwd's last partial workgroup returning early failed 32 of the 35 tests here (all
 but m0, m128, m32768, where no partial workgroup exists) and 11 older ones (test_render_train_grads, test_render_vs_oracle_bigger,
