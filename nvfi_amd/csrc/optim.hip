@@ -71,8 +71,8 @@ static int adam_impl(const nvfi_adam_tensor* t, int n_tensors, float beta1, floa
         int64_t nmax = 0;
         int k = base;
         for (; k < n_tensors && a.n < ADAM_MAX_T; ++k) {
+            if (t[k].n <= 0) continue;      // before the pointer check: an empty tensor has no storage, its pointers are NULL
             if (!t[k].p || !t[k].g || !t[k].m || !t[k].v) return nvfi_fail(2, "nvfi_adam_step: tensor %d has a NULL pointer", k);
-            if (t[k].n <= 0) continue;
             AdamT& T = a.t[a.n++];
             T.p = t[k].p; T.g = t[k].g; T.m = t[k].m; T.v = t[k].v; T.n = t[k].n;
             T.step_size = (float)((double)t[k].lr / bc1);

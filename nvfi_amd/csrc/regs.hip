@@ -5,7 +5,17 @@
 // (models/tensorf_keyframe.py:188-231) with utils.tensorf_utils.TVLoss (utils/tensorf_utils.py:139-158; t=True
 // multiplies the time-axis term by 3).  Planes are channel-last [H][W][C]: the x neighbour is +-C floats away,
 // the y neighbour +-W*C, so every load is coalesced across the channel/x index.
+//
+// The three values: every workgroup adds its partial sums - in double - to one slot of a small per-device scratch and takes a ticket; the
+// workgroup that arrives last rounds the three doubles to out3 once and clears the slot for its next use.  (Until this was in place the
+// workgroups added fp32 partials to out3 itself, 288 to 576 atomics per value in arrival order: three to four fp32 spacings of error on a
+// large grid, different from call to call.)  Calls take the slots of the ring in turn, so calls in flight on different streams do not share one.
 #include "common.h"
+#include <atomic>
+
+#define REG_SLOTS 64
+struct RegSlot { double acc[3]; unsigned ticket; unsigned pad; };
+#define REG_AGENT __HIP_MEMORY_SCOPE_AGENT
 
 struct RegJob {
     const float* p; float* g;
@@ -17,7 +27,7 @@ struct RegJob {
     float tv_w;         // TV weight (gradient scale multiplies the value scales)
     int tv_slot;        // 1: TV density, 2: TV app, 0: no TV
 };
-struct RegJobs { RegJob j[12]; int n; float* out; const float* wdev; };   // wdev (optional): device float[3] multipliers of the (L1, TV density, TV app) gradients
+struct RegJobs { RegJob j[12]; int n; float* out; const float* wdev; RegSlot* slot; };   // wdev (optional): device float[3] multipliers of the (L1, TV density, TV app) gradients
 
 // One thread handles 4 consecutive channels of a texel (C is a multiple of 4, so they share x and y): 16-byte loads of the
 // texel and its four neighbours, 32-bit index arithmetic (the largest plane has 1.9 M elements).
@@ -81,10 +91,20 @@ __global__ __launch_bounds__(1024) void k_plane_regs(RegJobs jobs) {
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = l1; red[1][threadIdx.x >> 6] = tv; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float s0 = 0.f, s1 = 0.f;
+        double s0 = 0.0, s1 = 0.0;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { s0 += red[0][w]; s1 += red[1][w]; }
-        if (J.l1_mode) atomicAdd(jobs.out + 0, J.l1_val * s0);
-        if (J.tv_slot) atomicAdd(jobs.out + J.tv_slot, s1);
+        RegSlot* S = jobs.slot;
+        if (J.l1_mode) __hip_atomic_fetch_add(&S->acc[0], (double)J.l1_val * s0, __ATOMIC_RELAXED, REG_AGENT);
+        if (J.tv_slot) __hip_atomic_fetch_add(&S->acc[J.tv_slot], s1, __ATOMIC_RELAXED, REG_AGENT);
+        // the ticket releases this workgroup's sums and, in the last workgroup, acquires everybody else's
+        if (__hip_atomic_fetch_add(&S->ticket, 1u, __ATOMIC_ACQ_REL, REG_AGENT) == gridDim.x * gridDim.y - 1u) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                jobs.out[i] = (float)__hip_atomic_load(&S->acc[i], __ATOMIC_RELAXED, REG_AGENT);
+                __hip_atomic_store(&S->acc[i], 0.0, __ATOMIC_RELAXED, REG_AGENT);
+            }
+            __hip_atomic_store(&S->ticket, 0u, __ATOMIC_RELEASE, REG_AGENT);
+        }
     }
 }
 
@@ -104,7 +124,16 @@ static int plane_regs(const nvfi_field_desc* f, float w_l1, float w_tv_density, 
                       const nvfi_grads* grads, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     RegJobs jobs; jobs.n = 0; jobs.out = out3; jobs.wdev = wdev;
-    if (launch_zero(out3, 3 * sizeof(float), st)) return 1;
+    // scratch of the value sums: allocated and cleared once per device (not inside a stream capture: run one call before capturing)
+    static PerDevice<RegSlot*> ring;
+    static std::atomic<unsigned> turn{0};
+    RegSlot** slots = ring.get([](RegSlot*& p, int) {
+        HIPCK(hipMalloc(&p, REG_SLOTS * sizeof(RegSlot)));
+        HIPCK(hipMemset(p, 0, REG_SLOTS * sizeof(RegSlot)));
+        return 0;
+    });
+    if (!slots) return 1;
+    jobs.slot = *slots + (turn.fetch_add(1u) % REG_SLOTS);
     const int A[3] = {0, 0, 1}, Bx[3] = {1, 2, 2}, Cc[3] = {2, 1, 0};
     auto add = [&](const float* p, float* g, int H, int W, int C, int l1_mode, int tv_slot, float hmul, float tvw) {
         RegJob& J = jobs.j[jobs.n++];
@@ -121,7 +150,7 @@ static int plane_regs(const nvfi_field_desc* f, float w_l1, float w_tv_density, 
         add(f->aps[i], grads ? grads->aps[i] : nullptr, f->G[Bx[i]], f->G[A[i]], f->Ca, 0, 2, 1.f, w_tv_app);
     }
     if ((f->Cd & 3) || (f->Ca & 3)) return nvfi_fail(2, "nvfi_plane_regs: channel counts must be multiples of 4");
-    // few, fat workgroups: every workgroup ends with two atomics on the same three floats (~11 ns each when contended)
+    // few, fat workgroups: every workgroup ends with two double atomics and a ticket on one scratch slot (~11 ns each when contended)
     hipLaunchKernelGGL(k_plane_regs, dim3(96, jobs.n), dim3(1024), 0, st, jobs);
     LAUNCHCK();
     return 0;

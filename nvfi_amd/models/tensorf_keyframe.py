@@ -248,7 +248,7 @@ class _RegFn(torch.autograd.Function):
     instead of ~230 torch launches each.  The kernel computes all three values in one pass over the planes, and a driver calls all three per
     iteration (train_nvfi.py:203-217), so:
       forward   the first call of an iteration runs the pass and keeps the value triple; the next two find the planes unchanged (same tensors,
-                same `_version`) and return their entry of it - one pass instead of three;
+                same `_version`, no fused-Adam step since) and return their entry of it - one pass instead of three;
       backward  with in-place gradient accumulation (arena / caller-owned .grad) the three nodes only deposit their upstream weights; the last
                 one - or the engine's end-of-backward callback, if the graph held fewer - runs ONE gradient pass with all of them
                 (nvfi_plane_regs_dev: weights read from device memory, no host sync).  Under pure autograd each node has to hand its own
@@ -258,7 +258,9 @@ class _RegFn(torch.autograd.Function):
     def forward(ctx, field, which, *planes):
         L = _lib.lib()
         rt = _rt(field)
-        key = tuple((p.data_ptr(), p._version) for p in planes)
+        from .. import optim as _optim
+        # nvfi_amd.optim.Adam moves the planes through raw pointers (no `_version` bump): its generation counter is part of the key, as in _frags
+        key = (tuple((p.data_ptr(), p._version) for p in planes), _optim.GENERATION)
         c = rt.get("_reg_fwd")
         if c is None or c[0] != key:
             # a new pass = a new iteration: whatever an aborted backward of the previous one left behind (deposited weights, a live count that

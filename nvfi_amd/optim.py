@@ -27,7 +27,7 @@ class Adam(torch.optim.Optimizer):
         [1/sqrt(1-beta2^t)] + [lr_k/(1-beta1^t) for every tensor k in table order] - for `step(hyper_dev=...)`: the caller uploads them
         and the (possibly hipGraph-captured) launch reads them from device memory.  Same values nvfi_adam_step derives on the host."""
         import numpy as np
-        out, head = [], None
+        out, head, states = [], None, []
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
@@ -36,16 +36,19 @@ class Adam(torch.optim.Optimizer):
                 st = self.state[p]
                 if len(st) == 0:
                     raise _lib.NvfiError("next_hyper() needs initialised state: run one ordinary step() first")
-                st["step"] = int(st["step"]) + 1
+                step = int(st["step"]) + 1
                 # nvfi_adam_step's arithmetic: betas and lr arrive there as C floats, the corrections are formed in double
                 b1f, b2f = float(np.float32(b1)), float(np.float32(b2))
-                bc1, bc2 = 1.0 - b1f ** float(st["step"]), 1.0 - b2f ** float(st["step"])
+                bc1, bc2 = 1.0 - b1f ** float(step), 1.0 - b2f ** float(step)
                 h = float(np.float32(1.0 / np.sqrt(bc2)))
                 if head is None:
-                    head = (h, st["step"], float(b1), float(b2))
-                elif head[1:] != (st["step"], float(b1), float(b2)):
+                    head = (h, step, float(b1), float(b2))
+                elif head[1:] != (step, float(b1), float(b2)):
                     raise _lib.NvfiError("step(hyper_dev=...) needs one (betas, step count) for all tensors")
                 out.append(float(np.float32(float(np.float32(group["lr"])) / bc1)))
+                states.append(st)
+        for st in states:       # only now: a refused call leaves every counter where it was
+            st["step"] = head[1]
         return [head[0]] + out
 
     @torch.no_grad()
