@@ -282,6 +282,21 @@ int nvfi_segloss(int64_t N, int K, const float* pc, const float* flow, const flo
                  const int32_t* rev_start, const int32_t* rev_edge, int loss_norm, float epsilon, float w_dynamic, float w_smooth,
                  float w_entropy, float grad_scale, int accumulate, float* gmask, float* losses4, float* R, float* t,
                  float* pc_transformed, void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- characteristic loss (an addition to ABI v5; csrc/charloss.hip; reference TensorVMKeyframeTimeKplane.characteristic_loss,
+ *      models/tensorf_keyframe.py:552-573): features stored at keyframe t_k, read at x, must equal the features of keyframe 0 read where x is
+ *      advected back to.  points (N,3) normalised.  t_k = round_half_even(clamp(t / ts, 0, K-1)) * ts for t > 0, else ts = tmax / (K-1) (the
+ *      reference's snap); x0 = nvfi_integrate_pos(points, t_k, 0) - the same launch path, x6 by default - written to points0_out when non-NULL.
+ *        loss[0] = mean_N (d_t - d_0)^2               d = compute_densityfeature at (points, row k) and at (x0, row 0)
+ *        loss[1] = mean_{N x app_dim} (a_t - a_0)^2   a = compute_appfeature (after basis_mat)
+ *      Both values are UN-weighted.  grads non-NULL: `weight` x the gradient of loss[0] + loss[1] is ACCUMULATED into grads->dps/dpt/aps/apt/basis
+ *      (a NULL member skips that tensor; no other member is read or written: nothing reaches the velocity nets, the warp is a constant as under
+ *      the reference's no_grad).  grads == NULL: value only.  t_k == 0: both values are exact zeros, x0 = points, no gradient is touched.
+ *      Value and gradients come out of the same pass; plane gradients are float atomics (NVFI_DETERMINISTIC does not cover this call).
+ *      Errors (2): N <= 0, use_vel == 0, K < 2, Cd != 24, Ca != 48, app_dim > 32. */
+int nvfi_char_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes);
+int nvfi_char_loss(const nvfi_field_desc* f, int64_t N, const float* points, float t, float weight,
+                   float* loss /* device float[2] */, float* points0_out /* (N,3) or NULL */, const nvfi_grads* grads /* or NULL */,
+                   void* workspace, int64_t workspace_bytes, void* stream);
 /* SHRender (models/tensorf_model_utils.py:292-296 with models/sh.py:87-110, degree 2): view (N,3), feat (N,27) -> rgb (N,3) */
 int nvfi_sh_render(int64_t N, const float* view, const float* feat27, float* rgb, void* stream);
 

@@ -66,6 +66,7 @@ EXPORTS = [
     "nvfi_segloss_workspace_bytes", "nvfi_knn_self", "nvfi_segloss",
     "nvfi_metrics_workspace_bytes", "nvfi_ssim", "nvfi_segm_confusion",
     "nvfi_render_flow", "nvfi_render_objects", "nvfi_render_fwd_select",
+    "nvfi_char_workspace_bytes", "nvfi_char_loss",
 ]
 
 _LIB = None
@@ -93,6 +94,8 @@ def lib():
         L.nvfi_render_flow.argtypes = [fp, C.c_int64, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
         L.nvfi_render_objects.argtypes = [fp, fp, C.c_int64, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp]
         L.nvfi_render_fwd_select.argtypes = [fp, fp, fp, C.c_int64, fp, fp, fp, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp, fp]
+        L.nvfi_char_workspace_bytes.argtypes = [fp, C.c_int64, i64p]
+        L.nvfi_char_loss.argtypes = [fp, C.c_int64, fp, C.c_float, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
         _LIB = L
     return _LIB
 

@@ -361,6 +361,53 @@ class _RegFn(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+class _CharFn(torch.autograd.Function):
+    """nvfi_char_loss computes the value AND the unit-weight gradients of its 13 tensors (twelve planes, basis_mat) in one pass, into a private
+    buffer; backward scales them by the upstream gradient (the pattern of _PdeFn)."""
+
+    @staticmethod
+    def forward(ctx, field, points, t, *params):
+        need = ctx.needs_input_grad[3:]
+        grads = _zero_grads(params, need) if any(need) else [None] * len(params)
+        terms, points0 = field._char_call(points, t, 1.0, grads if any(need) else None, params)
+        flat = next((g._base for g in grads if g is not None), None)
+        if flat is not None:
+            ctx.save_for_backward(flat)
+        ctx.field, ctx.need = field, list(need)
+        ctx.shapes = [(p.shape, p.stride()) for p in params]
+        ctx.mark_non_differentiable(terms, points0)
+        return terms[0] + terms[1], terms, points0
+
+    @staticmethod
+    def backward(ctx, g, _gt, _gp):
+        if not ctx.saved_tensors:
+            return (None,) * (3 + len(ctx.shapes))
+        field, saved = ctx.field, ctx.saved_tensors[0]
+        if field.accumulate_grads_inplace == "arena" and all(ctx.need):
+            params = field._render_params()[:13]
+            tgt = field._arena_attach(params, ctx.need)
+            a = _rt(field).get("_arena")
+            if tgt is not None and a is not None and all(x is y for x, y in zip(a["params"][:13], params)) and all(p.grad is a["views"].get(id(p)) for p in params):
+                # one launch: arena[planes, basis_mat] += g * (unit-weight gradients); a plain read-modify-write, so it is ordered against the
+                # atomic adds of the render backward on the field's side streams (_wait_writers / _note_writer), like _PdeFn's
+                field._wait_writers(True)
+                head = a["flat"][:saved.numel()]
+                head.addcmul_(saved, g.to(head.dtype).expand_as(head))
+                field._note_writer()
+                field._queue_join()
+                return (None,) * (3 + len(ctx.shapes))
+        flat = saved * g
+        out, o = [], 0
+        for (shp, strides), n in zip(ctx.shapes, ctx.need):
+            if not n:
+                out.append(None)
+                continue
+            k = shp.numel()
+            out.append(flat[o:o + k].as_strided(shp, strides))
+            o += (k + 63) // 64 * 64
+        return (None, None, None) + tuple(out)
+
+
 class TensorVMKeyframeTimeKplane(nn.Module):
     def __init__(self, aabb, gridSize, device, near_far, cfg):
         super().__init__()
@@ -1263,6 +1310,83 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         self.last_pde_out, self.last_pde_counters = out, counters
         self.last_pde_n_kept = None
         return out
+
+    # ------------------------------------------------------------------ characteristic loss (csrc/charloss.hip)
+    def characteristic_time(self, t):
+        """the keyframe time t_k the characteristic loss runs at (tensorf_keyframe.py:554-561, fp32): the nearest keyframe time for t > 0,
+        the first keyframe interval tmax / (K - 1) otherwise.  Host arithmetic; nvfi_char_loss derives the same number."""
+        K = int(self.num_keyframes)
+        t = np.float32(float(t))
+        if t > 0:
+            ts = np.float32(float(self.tmax) / (K - 1) if K > 1 else 1.0)
+            return float(np.rint(np.clip(t / ts, np.float32(0), np.float32(K - 1))) * ts)
+        return float(np.float32(float(self.tmax)) / np.float32(K - 1))
+
+    def _char_call(self, points, t, weight, grads, params=None):
+        """one nvfi_char_loss launch sequence -> (terms (2,), points0 (N,3)); grads: 13 tensors or None entries (dps, dpt, aps, apt, basis_mat)"""
+        if not self.use_vel:
+            raise _lib.NvfiError("characteristic_loss needs the velocity field (use_vel=False): there is nothing to advect the points with")
+        if not (self.aabb.is_cuda and points.is_cuda):
+            raise _lib.NvfiError("NVFi HIP kernels need the field and the points on the GPU (no CPU fallback exists)")
+        L = _lib.lib()
+        pts = points.detach().reshape(-1, 3).contiguous().float()
+        N = pts.shape[0]
+        desc = self._desc() if params is None else self._desc(list(params) + self._render_params()[13:])
+        nb = C.c_int64(0)
+        _lib.check(L.nvfi_char_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
+        ws = self._scratch("char", nb.value, pts.device)
+        terms = torch.empty(2, device=pts.device)
+        points0 = torch.empty_like(pts)
+        G = None
+        if grads is not None:
+            for g, p in zip(grads, self._render_params()[:13]):
+                if g is not None and g.stride() != p.stride():
+                    raise _lib.NvfiError("a gradient target must share the memory layout of its parameter (channels_last planes)")
+            G = C.byref(self._grads_struct(list(grads)))
+        _lib.check(L.nvfi_char_loss(C.byref(desc), C.c_int64(N), _lib.ptr(pts), C.c_float(float(t)), C.c_float(float(weight)), _lib.ptr(terms),
+                                    _lib.ptr(points0), G, _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        return terms, points0
+
+    def characteristic_loss_at(self, points, t, return_points0=False):
+        """characteristic_loss for caller-supplied normalised points (N,3): mean (d_t - d_0)^2 + mean (a_t - a_0)^2 between keyframe
+        t_k = characteristic_time(t) at `points` and keyframe 0 at points0 = integrate_pos(points, t_k, 0) (no gradient through the warp).  A 0-dim
+        tensor with autograd history onto the twelve planes and basis_mat; the two terms of the last call are kept in `last_char_terms`."""
+        if not self.use_vel:
+            raise _lib.NvfiError("characteristic_loss needs the velocity field (use_vel=False): there is nothing to advect the points with")
+        loss, terms, points0 = _CharFn.apply(self, points, float(t), *self._render_params()[:13])
+        self.last_char_terms = terms
+        return (loss, points0) if return_points0 else loss
+
+    def characteristic_loss(self, n_pts, t):
+        """tensorf_keyframe.py:552-573 with the semantics of its formula (t_k and the points as they were before the warp; the reference's own
+        call aliases both): n_pts points uniform in [-1,1]^3, drawn with torch.rand on the field's device."""
+        if not self.aabb.is_cuda:
+            raise _lib.NvfiError("NVFi HIP kernels need the field on the GPU (no CPU fallback exists)")
+        points = torch.rand(int(n_pts), 3, device=self.aabb.device) * 2 - 1
+        return self.characteristic_loss_at(points, t)
+
+    @torch.no_grad()
+    def characteristic_loss_backward_(self, points_or_n, t, weight=1.0):
+        """Fused value + backward of `weight * characteristic_loss`: the gradient is ACCUMULATED into the .grad of the twelve planes and
+        basis_mat (a tensor with requires_grad=False is left alone); returns the detached UN-weighted value (0-dim; `last_char_terms` holds
+        the density and the appearance term).  points_or_n: normalised points (N,3) or a point count (drawn as characteristic_loss does)."""
+        if not self.aabb.is_cuda:
+            raise _lib.NvfiError("NVFi HIP kernels need the field on the GPU (no CPU fallback exists)")
+        if isinstance(points_or_n, torch.Tensor):
+            points = points_or_n
+        else:
+            points = torch.rand(int(points_or_n), 3, device=self.aabb.device) * 2 - 1
+        grads = []
+        for p in self._render_params()[:13]:
+            if not p.requires_grad:
+                grads.append(None)
+                continue
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+            grads.append(p.grad)
+        terms, _ = self._char_call(points, t, weight, grads)
+        self.last_char_terms = terms
+        return terms[0] + terms[1]
 
     def _grads_struct_cached(self, ps):
         """nvfi_grads over the .grad tensors of the 31 render parameters (NULL for a parameter that is frozen or has no .grad): the ctypes
