@@ -317,6 +317,20 @@ typedef struct nvfi_adam_tensor { float* p; float* g; float* m; float* v; int64_
 /* F.mse_loss(x, target) of a training batch (train_nvfi.py:159,178) with its gradient in one launch: loss[0] = mean((x - target)^2),
  * grad[i] = 2 (x[i] - target[i]) / n.  One workgroup: n <= 2^22. */
 int nvfi_mse(const float* x, const float* target, int64_t n, float* loss, float* grad, void* stream);
+/* ---- depth supervision (an addition to ABI v5; csrc/depthloss.hip; reference utils/evaluation_utils.py:8-17 compute_depth_loss(pred, gt)):
+ *      with m the counted entries and n_c their number, med = LOWER median (sorted element (n_c - 1) / 2, torch.median's), s = mean|x - med|,
+ *      u = (pred - med_p) / (s_p + 1e-6), v = (target - med_t) / (s_t + 1e-6), loss[0] = mean((u - v)^2), UN-scaled.
+ *      g_pred[i] = grad_scale * d(loss)/d(pred[i]) with torch's rule for the median (its gradient is spread equally over all entries equal
+ *      to it, -0.0 == +0.0), exactly 0 at entries that do not count.  gt_index == NULL: gt is (n); else the target of entry i is gt[gt_index[i]]
+ *      (a whole depth image and the pixel_ids nvfi_draw_batch wrote; the indices are not range-checked).  NVFI_DEPTH_SKIP_HOLES: entry i counts
+ *      only if its target is finite and > 0.  n_c == 0: loss 0, gradient 0.  A NaN among the counted entries: loss and every counted gradient NaN.
+ *      n_counted: device int64[1] or NULL.  One launch of one workgroup, n <= 2^22; up to NVFI_DEPTH_LDS_MAX entries both maps are read once
+ *      and kept in LDS, above that every pass streams them.  Sums are fp64 in a fixed order: two calls on the same input give the same bits.
+ *      No global atomics, no memset, no host synchronisation.  Errors (2): n <= 0, n > 2^22, a NULL pointer, unknown flags. */
+#define NVFI_DEPTH_SKIP_HOLES 1
+#define NVFI_DEPTH_LDS_MAX 16384
+int nvfi_depth_loss(int64_t n, const float* pred, const float* gt, const int64_t* gt_index, int flags, float grad_scale,
+                    float* loss, float* g_pred, int64_t* n_counted, void* stream);
 int nvfi_adam_step(const nvfi_adam_tensor* t, int n_tensors, float beta1, float beta2, float eps, int64_t step, int zero_grad, void* stream);
 
 /* same step with the per-iteration scalars in DEVICE memory (hipGraph replay): hyper_dev[0] = 1/sqrt(1-beta2^step),

@@ -9,6 +9,8 @@ fp = C.c_void_p
 
 NVFI_TRAIN, NVFI_WHITE_BG, NVFI_TRANSFER, NVFI_WANT_MASK, NVFI_BWD_FORK, NVFI_WANT_FLOW, NVFI_WANT_SELECT = 1, 2, 4, 8, 16, 32, 64
 NCOUNTERS = 8
+NVFI_DEPTH_SKIP_HOLES = 1
+NVFI_DEPTH_LDS_MAX = 16384      # nvfi_depth_loss keeps both maps in LDS up to this many entries (include/nvfi_hip.h)
 
 
 class FieldDesc(C.Structure):
@@ -67,6 +69,7 @@ EXPORTS = [
     "nvfi_metrics_workspace_bytes", "nvfi_ssim", "nvfi_segm_confusion",
     "nvfi_render_flow", "nvfi_render_objects", "nvfi_render_fwd_select",
     "nvfi_char_workspace_bytes", "nvfi_char_loss",
+    "nvfi_depth_loss",
 ]
 
 _LIB = None
@@ -96,6 +99,7 @@ def lib():
         L.nvfi_render_fwd_select.argtypes = [fp, fp, fp, C.c_int64, fp, fp, fp, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp, fp]
         L.nvfi_char_workspace_bytes.argtypes = [fp, C.c_int64, i64p]
         L.nvfi_char_loss.argtypes = [fp, C.c_int64, fp, C.c_float, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
+        L.nvfi_depth_loss.argtypes = [C.c_int64, fp, fp, fp, C.c_int, C.c_float, fp, fp, fp, fp]
         _LIB = L
     return _LIB
 

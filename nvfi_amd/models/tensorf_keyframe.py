@@ -1403,14 +1403,25 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         return c[1]
 
     @torch.no_grad()
-    def render_mse_backward_(self, t, ray_o, ray_d, target, white_bg=True, loss_scale=1.0, jitter=None, wait_before_backward=None):
+    def render_mse_backward_(self, t, ray_o, ray_d, target, white_bg=True, loss_scale=1.0, jitter=None, wait_before_backward=None,
+                             target_depth=None, depth_index=None, depth_weight=1.0, skip_holes=False, check_depth_index=False):
         """Fused-driver form of one TRAINING render of train_nvfi.py:150-178 + its share of loss.backward() (train_nvfi.py:242):
         forward, `loss_scale * F.mse_loss(rgb_map, target)` and the backward of both, with the parameter gradients ACCUMULATED into p.grad
         (which must exist: nvfi_amd.dist.GradBucket, or zeros_like) - no autograd graph, no torch launch: nvfi_render_fwd_mse forms the loss and
         its gradient inside the composite kernel, nvfi_render_bwd_t takes it from there.  The counterpart of pde_loss_backward_ /
         regularizers_backward_ for the photometric term.  Returns (loss, rgb): a 0-dim device tensor with the UN-scaled mse and the (R,3) colours.
         wait_before_backward: a stream the backward half has to wait for (a driver that runs regularizers_backward_ - a plain read-modify-write of
-        the plane gradients - on a side stream beside the forward half)."""
+        the plane gradients - on a side stream beside the forward half).
+        target_depth (default None: nothing changes, the same launches and the same two return values): depth supervision, the reference's
+        `compute_depth_loss(depth_map, target_dpts)` (utils/evaluation_utils.py:8-17; Camera(..., dpt=) makes sample_rays return target_dpts).
+        One nvfi_depth_loss launch between the two halves reads the depth map of the forward and writes
+        `loss_scale * depth_weight * d(depth loss)/d(depth)`, which the backward half takes as its depth gradient - no torch launch.  Returns
+        (loss, rgb, depth_loss), depth_loss the UN-scaled, un-weighted value (0-dim device tensor).  target_depth is (R,) fp32, or - with
+        depth_index, the int64 pixel_ids of nvfi_draw_batch - a whole depth image read at depth_index[i] for ray i (no gather launch).  The
+        kernel does not range-check the indices: they are the caller's contract, as pixel_ids drawn for an image of target_depth's size are.
+        check_depth_index=True (a debugging aid: one torch min / max and a wait for it, before anything is launched) raises IndexError on an
+        index outside the image.  skip_holes=True counts ray i only if its target depth is finite and > 0.  Multi-GPU: every rank
+        normalises its OWN shard of the batch (its own medians); there is no global median."""
         L = _lib.lib()
         if not ray_o.is_cuda or not self.aabb.is_cuda:
             raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
@@ -1434,9 +1445,25 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         nbytes = C.c_int64(0)
         _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        a3, a1 = (3 * R + 63) // 64 * 64, (R + 63) // 64 * 64          # rgb | g_rgb | depth | acc | loss: one allocation, 256-byte aligned pieces
-        out = torch.empty(2 * a3 + 2 * a1 + 64, device=dev)
+        a3, a1 = (3 * R + 63) // 64 * 64, (R + 63) // 64 * 64          # rgb | g_rgb | depth | acc | loss [| g_depth]: one allocation, 256-byte aligned pieces
+        out = torch.empty(2 * a3 + 2 * a1 + 64 + (a1 if target_depth is not None else 0), device=dev)
         rgb, g_rgb, depth, acc, loss = out[:3 * R].view(R, 3), out[a3:a3 + 3 * R], out[2 * a3:2 * a3 + R], out[2 * a3 + a1:2 * a3 + a1 + R], out[2 * a3 + 2 * a1:]
+        g_depth = None
+        if target_depth is not None:
+            if not target_depth.is_cuda or (depth_index is not None and not depth_index.is_cuda):
+                raise _lib.NvfiError("NVFi HIP kernels need the depth target on the GPU (no CPU fallback exists)")
+            if target_depth.dtype != torch.float32 or not target_depth.is_contiguous():
+                raise ValueError("target_depth must be a contiguous float32 tensor")
+            if depth_index is not None:
+                if depth_index.dtype != torch.int64 or not depth_index.is_contiguous() or depth_index.numel() != R:
+                    raise ValueError(f"depth_index must be a contiguous int64 tensor with one entry per ray ({R})")
+                if check_depth_index:
+                    lo, hi = (int(v) for v in torch.aminmax(depth_index))
+                    if lo < 0 or hi >= target_depth.numel():
+                        raise IndexError(f"depth_index holds {lo if lo < 0 else hi}, outside the {target_depth.numel()} entries of target_depth")
+            elif target_depth.numel() != R:
+                raise ValueError(f"target_depth must hold one depth per ray ({R}) unless depth_index selects from an image")
+            g_depth = out[2 * a3 + 2 * a1 + 64:2 * a3 + 2 * a1 + 64 + R]
         weights = torch.empty(R, S, device=dev)
         counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
         st = _stream_ptr()
@@ -1444,11 +1471,17 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                                          C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
                                          _lib.ptr(counters), _lib.ptr(target), C.c_float(float(loss_scale)), _lib.ptr(loss), _lib.ptr(g_rgb), st))
         self.last_counters = counters
+        if g_depth is not None:       # loss[1]: the depth loss; the int64 count of the entries that took part sits behind it (loss[2:4])
+            _lib.check(L.nvfi_depth_loss(C.c_int64(R), _lib.ptr(depth), _lib.ptr(target_depth), _lib.ptr(depth_index),
+                                         C.c_int(_lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0), C.c_float(float(loss_scale) * float(depth_weight)),
+                                         _lib.ptr(loss[1:]), _lib.ptr(g_depth), _lib.ptr(loss[2:]), st))
         if wait_before_backward is not None:
             torch.cuda.current_stream().wait_stream(wait_before_backward)
         G = self._grads_struct_cached(ps)
         _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_int(int(t_dev is not None)),
-                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), None, None, None, C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
+                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, None, C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
+        if g_depth is not None:
+            return loss[0], rgb, loss[1]
         return loss[0], rgb
 
     def _jitter(self, R, device):

@@ -45,8 +45,80 @@ def load_model_checkpoint(cfg, ckpt, device):
     return nvfi, renderer
 
 
+def depth_loss_raw(pred, gt, gt_index=None, skip_holes=False, grad_scale=1.0, out=None, check_index=True):
+    """One nvfi_depth_loss launch (include/nvfi_hip.h) on flat fp32 device tensors, nothing else: -> (loss, g_pred, n_counted), a 0-dim
+    tensor with the UN-scaled loss, grad_scale * d(loss)/d(pred) (n,) and a 0-dim int64 tensor with the number of counted entries.
+    gt_index (int64, n): the target of entry i is gt[gt_index[i]].  The kernel does not range-check the indices, so this function does
+    (check_index=True: one min / max over the indices and a wait for it; an index outside gt raises IndexError before anything is launched).
+    check_index=False leaves that out - no torch launch, no wait - for indices that are known to be in range, and inside a hipGraph capture.
+    out: the three tensors to write into."""
+    import ctypes as C
+    from .. import _lib
+    if not (pred.is_cuda and gt.is_cuda and (gt_index is None or gt_index.is_cuda)):
+        raise _lib.NvfiError("NVFi HIP kernels need tensors on the GPU (no CPU fallback exists)")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32 or not pred.is_contiguous() or not gt.is_contiguous():
+        raise ValueError("depth_loss_raw takes contiguous float32 tensors")
+    n = pred.numel()
+    if gt_index is not None:
+        if gt_index.dtype != torch.int64 or not gt_index.is_contiguous() or gt_index.numel() != n:
+            raise ValueError(f"gt_index must be a contiguous int64 tensor of {n} entries")
+        if check_index and n:
+            lo, hi = (int(v) for v in torch.aminmax(gt_index))
+            if lo < 0 or hi >= gt.numel():
+                raise IndexError(f"gt_index holds {lo if lo < 0 else hi}, outside the {gt.numel()} entries of gt")
+    elif gt.numel() != n:
+        raise ValueError(f"pred has {n} entries, gt {gt.numel()}")
+    if out is None:
+        out = (torch.empty((), device=pred.device), torch.empty(n, device=pred.device), torch.empty((), dtype=torch.int64, device=pred.device))
+    loss, g_pred, n_counted = out
+    _lib.check(_lib.lib().nvfi_depth_loss(C.c_int64(n), _lib.ptr(pred), _lib.ptr(gt), _lib.ptr(gt_index),
+                                          C.c_int(_lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0), C.c_float(float(grad_scale)),
+                                          _lib.ptr(loss), _lib.ptr(g_pred), _lib.ptr(n_counted), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return loss, g_pred, n_counted
+
+
+class _DepthLossFn(torch.autograd.Function):
+    """value and gradient from one launch (nvfi_depth_loss, grad_scale = 1); backward is one scaling launch (the pattern of tensorf_utils._MseFn)"""
+
+    @staticmethod
+    def forward(ctx, pred, gt, skip_holes):
+        shape = pred.shape
+        loss, g_pred, _ = depth_loss_raw(pred.detach().reshape(-1).contiguous().float(), gt.detach().reshape(-1).contiguous().float(),
+                                         skip_holes=skip_holes)
+        ctx.save_for_backward(g_pred)
+        ctx.shape, ctx.dtype = shape, pred.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (g_pred,) = ctx.saved_tensors
+        return (g_pred * g).reshape(ctx.shape).to(ctx.dtype), None, None
+
+
+def compute_depth_loss(pred, gt, skip_holes=False):
+    """The reference's compute_depth_loss(pred, gt) (utils/evaluation_utils.py:8-17) on the GPU: each map is shifted by its median
+    (torch.median: the LOWER median) and scaled by its mean absolute deviation (+ 1e-6), the loss is the MSE of the normalised maps.  Any
+    shape, flattened; pred and gt must have the same number of entries.  One kernel launch forward (csrc/depthloss.hip, value and gradient),
+    one scaling launch backward.  The gradient follows torch autograd, including its rule for the median (spread equally over all entries
+    equal to it - every ray that hits nothing has depth == far).  Only `pred` receives a gradient: a `gt` that requires grad raises
+    NotImplementedError.  skip_holes=True counts entry i only if gt[i] is finite and > 0 (sensor depth maps mark missing pixels with 0);
+    the other entries get a gradient of exactly 0, and with nothing counted the loss is 0.  There is no CPU path: CPU tensors raise NvfiError.
+
+    The drop-in form `loss = mse + w * compute_depth_loss(depth_map, target_dpts)` works with the depth map of a training render (its
+    backward takes the depth gradient); the fused driver form is TensorVMKeyframeTimeKplane.render_mse_backward_(..., target_depth=).
+    Multi-GPU: every rank normalises its OWN shard of the batch (its own medians and deviations); there is no global median."""
+    from .. import _lib
+    if gt.requires_grad:
+        raise NotImplementedError("`gt` requires grad: only `pred` receives a gradient")
+    if not pred.is_cuda or not gt.is_cuda:
+        raise _lib.NvfiError("NVFi HIP kernels need tensors on the GPU (no CPU fallback exists)")
+    if pred.numel() != gt.numel():
+        raise ValueError(f"pred has {pred.numel()} entries, gt {gt.numel()}")
+    return _DepthLossFn.apply(pred, gt, bool(skip_holes))
+
+
 def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, near, far, white_background=True,
-                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False, with_flow=None):
+                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False, with_flow=None, gt_depths=None):
     """Eval driver (train_nvfi.py:395-459 without the dataset / wandb plumbing): optional `updateAlphaMask` at the current grid
     (`:413`), one `Renderer.render(mode='test')` per (pose, time) frame (`:437`), 8-bit PNGs named r_%03d.png (`:449-451`,
     written with PIL - imageio is not a dependency here) and per-frame / mean PSNR against `targets` (H,W,3 in [0,1]).
@@ -54,7 +126,10 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     Returns {"psnr": [..], "mean_psnr": float, "images": uint8 array (N,H,W,3)}.  with_ssim=True adds "ssim": [..] and "mean_ssim": the SSIM of
     every frame against its target (utils.metrics.ssim_frames: the kernel reads the (H,W,3) frames in place; the values come to the host once,
     after the loop).  with_flow=dt (default off) renders every frame through Renderer.render_flow instead - same rgb - and adds "flow2d"
-    (N,H,W,2), the optical flow over dt in pixels; with `savedir` its colour coding (utils.flow_vis.flow_to_rgb) is written as r_%03d_flow.png."""
+    (N,H,W,2), the optical flow over dt in pixels; with `savedir` its colour coding (utils.flow_vis.flow_to_rgb) is written as r_%03d_flow.png.
+    gt_depths (default off: N depth frames (H,W), 0 / inf / NaN where the sensor saw nothing) adds "depth_loss": [..] and "mean_depth_loss": the
+    median-normalised depth loss of every rendered depth map against its frame (compute_depth_loss with skip_holes=True: one launch per frame
+    on the 640 000 entries of an 800 x 800 frame; the values come to the host once, after the loop)."""
     import numpy as np
     from ..models import Camera
     from .metrics import mse2psnr, ssim_frames
@@ -62,17 +137,20 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     nvfi.eval()
     if update_alpha_mask:
         nvfi.nvfi.updateAlphaMask(nvfi.nvfi.gridSize)
-    imgs, psnrs, ssims, flows = [], [], [], []
+    imgs, psnrs, ssims, flows, dlosses = [], [], [], [], []
     with torch.no_grad():
         for idx in range(len(poses)):
             pose = torch.as_tensor(poses[idx], dtype=torch.float32, device=device)
             cam = Camera(pose, H, W, focal, None, near, far)
             if with_flow is None:
-                rgb = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test")[0]
+                res = renderer.render(float(times[idx]), cam.rays.to(device), white_background=white_background, mode="test")
+                rgb = res[0]
             else:
                 res = renderer.render_flow(float(times[idx]), cam.rays.to(device), float(with_flow), camera=cam, white_background=white_background)
                 rgb = res[0]
                 flows.append(res[6].reshape(H, W, 2))
+            if gt_depths is not None:
+                dlosses.append(compute_depth_loss(res[1], torch.as_tensor(gt_depths[idx], dtype=torch.float32, device=device), skip_holes=True))
             rgb = rgb.reshape(H, W, 3)
             if targets is not None:
                 tgt = torch.as_tensor(targets[idx], dtype=torch.float32, device=device).reshape(H, W, 3)
@@ -98,6 +176,9 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     if with_ssim:
         out["ssim"] = torch.cat(ssims).cpu().tolist() if ssims else []
         out["mean_ssim"] = (sum(out["ssim"]) / len(out["ssim"])) if ssims else None
+    if gt_depths is not None:
+        out["depth_loss"] = torch.stack(dlosses).cpu().tolist() if dlosses else []
+        out["mean_depth_loss"] = (sum(out["depth_loss"]) / len(out["depth_loss"])) if dlosses else None
     return out
 
 
