@@ -48,6 +48,9 @@ extern "C" int nvfi_stream_capture_id(void* stream, uint64_t* id) {
 }
 
 // ---------------------------------------------------------------- VelBasis evaluation
+// ONE published size for the workspaces of nvfi_vel_eval (both nets' fragments) and nvfi_integrate_pos (PosPlan below); nvfi_char_loss nests it
+static_assert(VEL_FRAG_FLOATS * 4 % 256 == 0 && VEL_FRAG_FLOATS * 4 + 4096 >= X6_IMAGE_BYTES + 256,
+              "nvfi_vel_workspace_bytes covers PosPlan: one fragment set, N float4 (up to 240 bytes of padding behind them) and the x6 image");
 extern "C" int nvfi_vel_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes) {
     (void)f;
     *bytes = align_up((int64_t)2 * VEL_FRAG_FLOATS * 4 + 4096 + N * 16 + N * 12, 256);
@@ -61,60 +64,50 @@ extern "C" int nvfi_vel_eval(const nvfi_field_desc* f, int64_t N, const float* x
     float* fv = B.take<float>(VEL_FRAG_FLOATS);
     float* fa = B.take<float>(VEL_FRAG_FLOATS);
     if (B.off > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)B.off);
-    PackJobs jobs; jobs.n = 0;
+    VelImages VI;
+    if (int rc = vel_images(f, gated ? VI_VEL : VI_VEL | VI_ANET, VelImageRoom{fv, fa}, &VI, nullptr, 0, st)) return rc;
     VelEvalArgs a; memset(&a, 0, sizeof(a));
-    if (pack_vel_frags(f->vW, f->vb, fv, &a.Wv, &jobs)) return 3;
-    if (!gated) { if (pack_vel_frags(f->aW, f->ab, fa, &a.Wa, &jobs)) return 3; }
-    if (launch_pack(jobs, st)) return 1;
-    a.f = *f; a.N = N; a.xt = xt; a.u6 = u6; a.gated = gated;
+    a.f = *f; a.Wv = VI.VW; a.Wa = VI.AW; a.N = N; a.xt = xt; a.u6 = u6; a.gated = gated;
     return launch_vel_eval(a, st);
 }
 
 // ---------------------------------------------------------------- integrate_pos (per-point times)
-static bool nograd_x6_default(const nvfi_field_desc* f) { return sw(NVFI_INTEGRATE_X6) != 0 && !(f->vel_fp16 & 8); }
 __global__ void k_pack_xt(int64_t N, const float* x, float4* xw) {
     int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i < N) xw[i] = make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], 0.f);
+}
+// fv: the fp32 fragments (WARP_FP32) or the fp16 images, hi + lo (WARP_FP16IN); x6img: the call's own x6 image (own_x6: WARP_X6 without a fragment cache)
+struct PosPlan { float* fv; float4* xw; float* x6img; int64_t total; };
+static_assert(VEL_FRAG_FLOATS * 4 >= 2 * PRE16_IMAGE_BYTES, "fragment region holds the fp16 images (hi + lo)");
+static void plan_pos(int64_t N, bool own_x6, void* ws, PosPlan* P) {
+    Bump B{(char*)ws, 0, 0};
+    P->fv = B.take<float>(VEL_FRAG_FLOATS);
+    P->xw = B.take<float4>(N);
+    P->x6img = own_x6 ? B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
+    P->total = B.off;
 }
 extern "C" int nvfi_integrate_pos(const nvfi_field_desc* f, int64_t N, const float* x, const float* t, const float* base,
                                   float* xk, void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (N <= 0) return 0;
-    Bump B{(char*)workspace, 0, 0};
-    float* fv = B.take<float>(VEL_FRAG_FLOATS);
-    float4* xw = B.take<float4>(N);
-    if (B.off > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)B.off);
-    // round 6: x6 (vel_x6w.hip: fp32 products of the hidden layers formed exactly on the 16-bit matrix pipe; as accurate against float64 as the
-    // fp32 MFMA kernels, tests/test_gpu_x6.py) is the DEFAULT of every no-grad back-advection, as it already was for eval renders and the
-    // PDE prefilter; vel_fp16 bit 3 (+8) or NVFI_INTEGRATE_X6=0 keep the fp32 MFMA kernel of vel.hip (the A/B reference of the tests)
-    if ((f->vel_fp16 & 3) == 3 || ((f->vel_fp16 & 3) == 0 && nograd_x6_default(f))) {
-        const float* img = nullptr;
-        if (f->frags) { FragCache FC; frag_cache_layout(f->frags, &FC); img = (const float*)FC.vel_x6; }
-        else {
-            float* own = B.take<float>(X6_IMAGE_BYTES / 4);
-            if (B.off > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)B.off);
-            if (launch_pack_x6(f->vW, own, st)) return 1;
-            img = own;
-        }
-        hipLaunchKernelGGL(k_pack_xt, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, xw);
+    const WarpKind kind = warp_kind(f, false, true);
+    PosPlan P; plan_pos(N, kind == WARP_X6 && !f->frags, workspace, &P);
+    if (P.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)P.total);
+    VelImages VI;
+    if (int rc = vel_images(f, kind == WARP_X6 ? VI_X6 : (kind == WARP_FP32 ? VI_VEL : 0), VelImageRoom{P.fv, nullptr, nullptr, nullptr, nullptr, P.x6img}, &VI, nullptr, 0, st)) return rc;
+    hipLaunchKernelGGL(k_pack_xt, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, P.xw);
+    if (kind == WARP_X6) {
         X6Args xa; memset(&xa, 0, sizeof(xa));
-        xa.f = *f; xa.img = img; xa.n_direct = N; xa.xw = xw; xa.xout3 = xk; xa.pt_t = t; xa.pt_base = base; xa.dt_max = dt_max_of(*f); xa.max_steps = 4096;
+        xa.f = *f; xa.img = VI.x6; xa.n_direct = N; xa.xw = P.xw; xa.xout3 = xk; xa.pt_t = t; xa.pt_base = base; xa.dt_max = dt_max_of(*f); xa.max_steps = 4096;
         return launch_rk2_x6(xa, N, st);
     }
-    PackJobs jobs; jobs.n = 0;
-    Rk2Args a; memset(&a, 0, sizeof(a));
-    if (!(f->vel_fp16 & 3)) {
-        if (pack_vel_frags(f->vW, f->vb, fv, &a.Wv, &jobs)) return 3;
-        if (launch_pack(jobs, st)) return 1;
-    }
-    hipLaunchKernelGGL(k_pack_xt, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, xw);
-    if (f->vel_fp16 & 3) {      // opt-in fp16-input inference mode (pre16.hip): the fragment region of the workspace holds the fp16 image
-        static_assert(VEL_FRAG_FLOATS * 4 >= 2 * PRE16_IMAGE_BYTES, "fragment region holds the fp16 images (hi + lo)");
+    if (kind == WARP_FP16IN) {      // opt-in fp16-input inference mode (pre16.hip): the fragment region of the workspace holds the fp16 image
         Rk16Args h; memset(&h, 0, sizeof(h));
-        h.img = fv; h.P = N; h.xw = xw; h.xout3 = xk; h.pt_t = t; h.pt_base = base; h.dt_max = dt_max_of(*f); h.max_steps = 4096;
+        h.img = P.fv; h.P = N; h.xw = P.xw; h.xout3 = xk; h.pt_t = t; h.pt_base = base; h.dt_max = dt_max_of(*f); h.max_steps = 4096;
         return launch_rk2_inf16(f, h, false, st);
     }
-    a.f = *f; a.count = nullptr; a.n_direct = N; a.list = nullptr; a.xw = xw; a.xout = xk;
+    Rk2Args a; memset(&a, 0, sizeof(a));
+    a.f = *f; a.Wv = VI.VW; a.count = nullptr; a.n_direct = N; a.list = nullptr; a.xw = P.xw; a.xout = xk;
     a.pt_t = t; a.pt_base = base; a.dt_max = dt_max_of(*f); a.max_steps = 4096;
     return launch_rk2_fwd(a, N, false, st);
 }
@@ -158,47 +151,37 @@ extern "C" int nvfi_compute_alpha(const nvfi_field_desc* f, int64_t N, const flo
     if (N >= (1ll << 31) - 256) return nvfi_fail(2, "N too large for one call; chunk the points");
     AlphaPlan AP; plan_alpha(N, workspace, &AP);
     float* fv = AP.fv; float4* xw = AP.xw; float* sig = AP.sig;
-    struct { int64_t off; } B{AP.total};
-    if (B.off > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)B.off);
-    const float base = transfer ? 0.f : snap_base(*f, t);
+    if (AP.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)AP.total);
+    // the uniform step sequence back to the keyframe: the render's own schedule (0: t is a keyframe time or the field has no velocity net)
+    Rk2Args a; memset(&a, 0, sizeof(a));
+    float base;
+    const int n = rk_schedule(*f, t, transfer ? NVFI_TRANSFER : 0, &base, a.dt, a.tcur);
+    const WarpKind kind = warp_kind(f, false, true);
     const unsigned nb = (unsigned)((N + 255) / 256);
     hipLaunchKernelGGL(k_alpha_prep, dim3(nb), dim3(256), 0, st, *f, N, xyz_world, norm_time(*f, base), xw);
-    if (f->use_vel && !is_close(t, base) && ((f->vel_fp16 & 3) == 3 || ((f->vel_fp16 & 3) == 0 && nograd_x6_default(f)))) {
+    VelImages VI;
+    if (n != 0 && kind == WARP_X6) {
         // round 6: the x6 kernel with per-point times (all equal here; the kernel runs integrate_pos' own fp32 recurrence dt = sign * min(|off|,
-        // dt_max) per point - the numbers the host loop below derives).  tt / tb: 2 N floats behind the plan (nvfi_alpha_workspace_bytes)
+        // dt_max) per point: the schedule's numbers, without its limit of MAX_RK_STEPS).  tt / tb: 2 N floats behind the plan (nvfi_alpha_workspace_bytes)
         float* tt = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + AP.total);
         float* tb = tt + N;
         if (AP.total + 2 * N * (int64_t)sizeof(float) > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)(AP.total + 8 * N));
-        const float* img = nullptr;
-        if (f->frags) { FragCache FC; frag_cache_layout(f->frags, &FC); img = (const float*)FC.vel_x6; }
-        else { if (launch_pack_x6(f->vW, AP.x6img, st)) return 1; img = AP.x6img; }
+        if (int rc = vel_images(f, VI_X6, VelImageRoom{nullptr, nullptr, nullptr, nullptr, nullptr, AP.x6img}, &VI, nullptr, 0, st)) return rc;
         hipLaunchKernelGGL(k_alpha_times, dim3(nb), dim3(256), 0, st, N, t, base, tt, tb);
         X6Args xa; memset(&xa, 0, sizeof(xa));
-        xa.f = *f; xa.img = img; xa.n_direct = N; xa.xw = xw; xa.pt_t = tt; xa.pt_base = tb; xa.dt_max = dt_max_of(*f); xa.max_steps = 4096;
+        xa.f = *f; xa.img = VI.x6; xa.n_direct = N; xa.xw = xw; xa.pt_t = tt; xa.pt_base = tb; xa.dt_max = dt_max_of(*f); xa.max_steps = 4096;
         if (launch_rk2_x6(xa, N, st)) return 1;
-    } else if (f->use_vel && !is_close(t, base)) {
-        Rk2Args a; memset(&a, 0, sizeof(a));
-        const float dtm = dt_max_of(*f);
-        float off = t - base, tc = t;
-        int n = 0;
-        while (fabsf(off) > 0.f) {
-            if (n >= MAX_RK_STEPS) return nvfi_fail(2, "t=%g needs more than %d RK2 steps", t, MAX_RK_STEPS);
-            const float m = fabsf(off) < dtm ? fabsf(off) : dtm;
-            const float dt = off > 0.f ? m : -m;
-            a.dt[n] = dt; a.tcur[n] = tc;
-            off = off - dt; tc = tc - dt; ++n;
-        }
-        if (f->vel_fp16 & 3) {  // opt-in fp16-input inference mode (pre16.hip)
+    } else if (n != 0) {
+        if (n < 0) return nvfi_fail(2, "t=%g needs more than %d RK2 steps", t, MAX_RK_STEPS);
+        if (kind == WARP_FP16IN) {  // opt-in fp16-input inference mode (pre16.hip)
             Rk16Args h; memset(&h, 0, sizeof(h));
             h.img = fv; h.P = N; h.xw = xw; h.xout = xw; h.nsteps = n;
             for (int k = 0; k < n; ++k) { h.dt[k] = a.dt[k]; h.tcur[k] = a.tcur[k]; }
             if (launch_rk2_inf16(f, h, true, st)) return 1;
         } else {
-        PackJobs jobs; jobs.n = 0;
-        if (pack_vel_frags(f->vW, f->vb, fv, &a.Wv, &jobs)) return 3;
-        if (launch_pack(jobs, st)) return 1;
-        a.f = *f; a.count = nullptr; a.n_direct = N; a.list = nullptr; a.xw = xw; a.xout = nullptr; a.nsteps = n;
-        if (launch_rk2_fwd(a, N, true, st)) return 1;
+            if (int rc = vel_images(f, VI_VEL, VelImageRoom{fv}, &VI, nullptr, 0, st)) return rc;
+            a.f = *f; a.Wv = VI.VW; a.count = nullptr; a.n_direct = N; a.list = nullptr; a.xw = xw; a.xout = nullptr; a.nsteps = n;
+            if (launch_rk2_fwd(a, N, true, st)) return 1;
         }
     }
     {   // density at the (warped) points with the quad-lane gather kernel (scatter.hip), then alpha = 1 - exp(-sigma * length)

@@ -148,31 +148,25 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
     a.vel_map = vel_map; a.flow_map = flow_map; a.flow2d = flow2d;
     hipLaunchKernelGGL(k_flow_gather, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
     LAUNCHCK();
-    FragCache FC; const bool cached = f->frags != nullptr;
-    if (cached) frag_cache_layout(f->frags, &FC);
-    const bool x6 = vf == 3 || (sw(NVFI_INTEGRATE_X6) != 0 && !(f->vel_fp16 & 8));
-    VelFrags VW;
-    if (vel_map || (want_flow && !x6)) {
-        PackJobs jobs; jobs.n = 0;
-        if (pack_vel_frags(f->vW, f->vb, cached ? FC.vel : P.vel_frag, &VW, &jobs)) return 3;
-        if (!cached && launch_pack(jobs, st)) return 1;
-    }
+    // (vf is 0 or 3 here: WARP_X6 or WARP_FP32)
+    const bool x6 = warp_kind(f, false, true) == WARP_X6, warp = want_flow && t1 != t;
+    const unsigned need = ((vel_map || (want_flow && !x6)) ? VI_VEL : 0) | ((warp && x6) ? VI_X6 : 0);
+    VelImages VI;
+    if (int rc2 = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, nullptr, nullptr, nullptr, P.flow_x6}, &VI, nullptr, 0, st)) return rc2;
     if (vel_map) {
         VelEvalArgs va; memset(&va, 0, sizeof(va));
-        va.f = *f; va.Wv = VW; va.N = N; va.count = count_m; va.xt = reinterpret_cast<const float*>(P.flow_xt);
+        va.f = *f; va.Wv = VI.VW; va.N = N; va.count = count_m; va.xt = reinterpret_cast<const float*>(P.flow_xt);
         va.u6 = reinterpret_cast<float*>(P.flow_vg); va.u_stride = 4; va.gated = 1;
         if (launch_vel_eval(va, st)) return 1;
     }
-    if (want_flow && t1 != t) {
+    if (warp) {
         if (x6) {
-            const void* img = cached ? FC.vel_x6 : (const void*)P.flow_x6;
-            if (!cached && launch_pack_x6(f->vW, P.flow_x6, st)) return 1;
             X6Args xa; memset(&xa, 0, sizeof(xa));
-            xa.f = *f; xa.img = img; xa.count = count_m; xa.xw = P.flow_xd; xa.pt_t = P.flow_tb; xa.pt_base = P.flow_tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
+            xa.f = *f; xa.img = VI.x6; xa.count = count_m; xa.xw = P.flow_xd; xa.pt_t = P.flow_tb; xa.pt_base = P.flow_tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
             if (launch_rk2_x6(xa, N, st)) return 1;
         } else {
             Rk2Args ra; memset(&ra, 0, sizeof(ra));
-            ra.f = *f; ra.Wv = VW; ra.count = count_m; ra.xw = P.flow_xd; ra.pt_t = P.flow_tb; ra.pt_base = P.flow_tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
+            ra.f = *f; ra.Wv = VI.VW; ra.count = count_m; ra.xw = P.flow_xd; ra.pt_t = P.flow_tb; ra.pt_base = P.flow_tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
             if (launch_rk2_fwd(ra, N, false, st)) return 1;
         }
     }

@@ -1,4 +1,5 @@
-// frags.h - persistent fragment cache of a field (round 5, ABI v5: nvfi_field_desc.frags)
+// frags.h - the packed weight images of a field: the persistent fragment cache (round 5, ABI v5: nvfi_field_desc.frags) and the ONE way a
+// host entry point gets the velocity net's images (vel_images) and learns which warp kernel it is about to launch (warp_kind)
 //
 // The MFMA kernels read the Linear weights in fragment order (engine.h).  Rounds 1-4 repacked them inside every call into the call's
 // workspace - 3 k_pack + 4 k_frag_x4 launches per training iteration for weights that change once per iteration.  nvfi_pack_frags writes
@@ -11,37 +12,29 @@
 #include "pde.h"
 #include "x6.h"
 
-#define A_X4B_FLOATS (4 * X4_FLOATS(4, 64) + X4_FLOATS(4, 4))      // transposed x4 fragments t[1..5] of a_weight_net (pde_fuse.hip)
-struct FragCache { float *render, *vel, *anet, *vel_x4f, *vel_x4b, *a_x4b; void* vel_x6; void* vel_x6t; int64_t total; };
-static inline void frag_cache_layout(const float* base, FragCache* c) {
-    Bump B{(char*)base, 0, 0};
-    c->render = B.take<float>(RENDER_FRAG_FLOATS);
-    c->vel = B.take<float>(VEL_FRAG_FLOATS);
-    c->anet = B.take<float>(VEL_FRAG_FLOATS);
-    c->vel_x4f = B.take<float>(VEL_X4F_FLOATS);
-    c->vel_x4b = B.take<float>(VEL_X4B_FLOATS);
-    c->a_x4b = B.take<float>(A_X4B_FLOATS);
-    c->vel_x6 = B.take<float>(X6_IMAGE_BYTES / 4);         // the three bfloat16 images of weight_net's layers 0..4 (vel_x6.hip)
-    c->vel_x6t = B.take<float>(X6_IMAGE_BYTES / 4);        // ... and of their transposes (round 6: the dgrad of vel_fuse.hip on x6)
-    c->total = align_up(B.off, 256);
-}
-// pointer tables into the x4 regions (the layouts pack_vel_x4_fwd / pack_vel_x4_bwd write)
-static inline void x4f_pointers(const float* buf, const float4** f4) {
-    const float* p = buf;
-    f4[0] = reinterpret_cast<const float4*>(p); p += X4_FLOATS(4, 14);
-    for (int l = 1; l <= 4; ++l) { f4[l] = reinterpret_cast<const float4*>(p); p += X4_FLOATS(4, 64); }
-    f4[5] = reinterpret_cast<const float4*>(p);
-}
-static inline void x4b_pointers(const float* buf, const float4** t4) {      // T0 (1 tile x 64 steps), t1..t4, t5 (4 tiles x 4 steps)
-    const float* p = buf;
-    t4[0] = reinterpret_cast<const float4*>(p); p += X4_FLOATS(1, 64);
-    for (int l = 1; l <= 4; ++l) { t4[l] = reinterpret_cast<const float4*>(p); p += X4_FLOATS(4, 64); }
-    t4[5] = reinterpret_cast<const float4*>(p);
-}
-static inline void a_x4b_pointers(const float* buf, const float4** ta4) {   // t1..t4, t5 of a_weight_net
-    const float* p = buf;
-    ta4[0] = nullptr;
-    for (int l = 1; l <= 4; ++l) { ta4[l] = reinterpret_cast<const float4*>(p); p += X4_FLOATS(4, 64); }
-    ta4[5] = reinterpret_cast<const float4*>(p);
-}
+// ---------------------------------------------------------------- the velocity net's images
+// VI_VEL / VI_ANET: the plain MFMA fragments (VelFrags) of weight_net / a_weight_net; VI_X4F / VI_X4B: x4 copies of weight_net's forward /
+// transposed fragments; VI_A_X4B: of a_weight_net's transposed fragments; VI_X6 / VI_X6T: the three-term bfloat16 image of weight_net / its transpose
+enum { VI_VEL = 1, VI_ANET = 2, VI_X4F = 4, VI_X4B = 8, VI_A_X4B = 16, VI_X6 = 32, VI_X6T = 64 };
+struct VelImageRoom { float *vel, *anet, *x4f, *x4b, *a_x4b; void *x6, *x6t; };     // the call's own workspace, NULL where its plan has none
+struct VelImages { VelFrags VW, AW; const float4 *f4[6], *t4[6], *ta4[6]; const void *x6, *x6t; };
+// The images `need` names, and nothing else, in *out.  With f->frags they are the cache's and nothing is launched.  Without, they are packed into
+// `room` with the per-call pack kernels - one k_pack for the plain fragments, one k_frag_x4 for weight_net's x4 copies, one for a_weight_net's,
+// one x6 pack - except those `have` names: the room holds them already (the render backward behind its forward).  An image that is needed, not
+// cached and has no room is error 3 naming it.  ride: plain pack jobs of the caller (the render MLP's) that share the k_pack launch of an
+// uncached call, or NULL; a cached call's are dropped, as its fragments are the cache's too (render_frag_room).
+int vel_images(const nvfi_field_desc* f, unsigned need, const VelImageRoom& room, VelImages* out, const PackJobs* ride, unsigned have, hipStream_t st);
+// where the render MLP's fragments of a call live: the cache's region, or the call's own room
+float* render_frag_room(const nvfi_field_desc* f, float* own);
+
+// ---------------------------------------------------------------- which kernel warps the samples back to the keyframe
+enum WarpKind { WARP_X6, WARP_FP16IN, WARP_FP32 };
+// per_point: the no-grad integrators with per-point times (nvfi_integrate_pos, nvfi_compute_alpha, nvfi_render_flow); otherwise the render's
+// warp on its uniform step sequence, in training (train) or eval mode.  The table stands beside the definition (frags.hip).
+WarpKind warp_kind(const nvfi_field_desc* f, bool train, bool per_point);
+// the render plan has room for the fp16 images: a WARP_FP16IN render, and an eval render with vel_fp16 = 3, which has always carried it (pinned sizes)
+bool warp_fp16_room(const nvfi_field_desc* f, bool train);
+// the training warp writes the z rows of layers 0..3 as x4 stash blocks (x6 forward + fused adjoint, NVFI_RK2_X4): forward and backward both ask here
+bool warp_stash_x4(const nvfi_field_desc* f);
+
 int launch_pack_all(const PackJobsAll& jobs, const X6PackArgs* x6, hipStream_t st);

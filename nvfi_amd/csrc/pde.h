@@ -27,11 +27,13 @@ struct PdePrepArgs {
     int* cls; int* rank; int* cls_count;
 };
 
-// x4 fragment repack jobs (pde_jet.hip): four consecutive K steps of a lane side by side, so one 16-byte load feeds four MFMA steps
+// x4 fragment repack jobs (k_frag_x4, pde_jet.hip; built by vel_images, frags.hip): four consecutive K steps of a lane side by side, so one 16-byte load feeds four MFMA steps
 struct X4Jobs { const float* src[12]; float* dst[12]; int MT[12]; int NS[12]; int n; };
 #define X4_FLOATS(MT, NS) ((MT) * (((NS) + 3) / 4) * 256)
-// v-net fragments in x4 order: forward f[0] (4 tiles x 14 steps), f[1..4] (4 x 64), f[5] (1 x 64); transposed t[1..4], t[5] (4 x 4)
-#define VEL_X4_FLOATS (X4_FLOATS(4, 14) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(1, 64) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(4, 4))
+// sizes of the x4 sets (their layouts: frags.hip): weight_net's forward fragments, its transposed ones, a_weight_net's transposed t[1..5]
+#define VEL_X4F_FLOATS (X4_FLOATS(4, 14) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(1, 64))
+#define VEL_X4B_FLOATS (X4_FLOATS(1, 64) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(4, 4))
+#define A_X4B_FLOATS (4 * X4_FLOATS(4, 64) + X4_FLOATS(4, 4))
 
 // bookkeeping done by the last workgroup of k_pde_seeds (round 5; ticket == NULL: the separate k_pde_pass_count / _finish / _counters launches)
 struct PdeTail {
@@ -72,16 +74,11 @@ struct SplitArgs {
 };
 int launch_rk2_split(const SplitArgs& a, int64_t cap_points, hipStream_t st);
 // the render warp on the same layout (uniform step sequence, optional training stash)
-#define VEL_X4F_FLOATS (X4_FLOATS(4, 14) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(1, 64))     // forward fragments only
 struct SplitUniArgs { Rk2Args r; const float4* f4[6]; const float* bv[6]; };
 int launch_rk2_split_uni(const SplitUniArgs& a, int64_t cap_samples, bool stash, hipStream_t st);
 // the adjoint (vel_split.hip: k_rk2_split_bwd); t4[0] = T0 (1 tile x 64 steps), t4[1..4], t4[5] (4 tiles x 4 steps)
-#define VEL_X4B_FLOATS (X4_FLOATS(1, 64) + 4 * X4_FLOATS(4, 64) + X4_FLOATS(4, 4))
 struct SplitBwdArgs { Rk2Args r; const float4* t4[6]; };
 int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st);
-int pack_vel_x4_bwd(const VelFrags& W, float* buf, const float4** t4, hipStream_t st);
-// x4 copies of the forward fragments of a packed VelFrags into buf (VEL_X4F_FLOATS); fills f4[6]
-int pack_vel_x4_fwd(const VelFrags& W, float* buf, const float4** f4, hipStream_t st);
 
 // opt-in fp16 pre-pass of the prefilter (pre16.hip)
 #define PRE16_IMAGE_BYTES 150528   // fp16 fragments of the six weight_net layers (144 KB) + fp32 biases: staged into LDS once per workgroup
@@ -118,10 +115,10 @@ int launch_pde_jet_bwd(const PdeJetArgs& a, unsigned tiles, unsigned anet_wgs, h
 // pde_jet6.hip (round 6): the forward with the hidden layers on the 16-bit matrix pipe (x6img: the three bfloat16 weight images of x6.h)
 int launch_pde_jet6_fwd(const PdeJetArgs& a, const void* x6img, unsigned tiles, unsigned anet_wgs, hipStream_t st);
 
-// value adjoint with the correction term; no input gradient needed
-template <int ACT, bool CORR>
+// value adjoint of a net whose Jacobian is not taken (a_weight_net); no input gradient needed
+template <int ACT>
 __device__ __forceinline__ void velnet_value_backward(const VelFrags& W, float* lds_w, float* lds_b, int lane, const float* seed4,
-                                                      const float* zst, const float* corr, float* gst) {
+                                                      const float* zst, float* gst) {
     float g[64];
     f32x16 acc[4];
     g[0] = seed4[0]; g[1] = seed4[1]; g[2] = seed4[2]; g[3] = seed4[3];
@@ -143,12 +140,7 @@ __device__ __forceinline__ void velnet_value_backward(const VelFrags& W, float* 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int s = 16 * m + r;
-                float v = act_d1<ACT>(zl[s * REGF + lane]) * acc[m][r];
-                if (CORR) {
-                    const float* c0 = corr + (size_t)l * 64 * REGF + s * REGF + lane;
-                    v += (c0[0] + c0[(size_t)320 * REGF]) + (c0[(size_t)640 * REGF] + c0[(size_t)960 * REGF]);
-                }
-                g[s] = v;
+                g[s] = act_d1<ACT>(zl[s * REGF + lane]) * acc[m][r];
             }
         stash_store<64>(gst + (size_t)l * 64 * REGF, lane, g);
         if (l >= 1) {

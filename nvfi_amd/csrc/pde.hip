@@ -7,9 +7,11 @@
 //   and loss.backward() through the Jacobian (second order).
 //
 // MI355X design: the Jacobian is computed in FORWARD mode (value + 4 tangents pushed through the
-// MFMA engine, activations register-resident), the backward is the hand-written reverse of that
-// tangent program (4 tangent-adjoint passes feeding a second-derivative correction into the
-// value-adjoint pass), and weight gradients are split-K MFMA over the stashed tiles (k_wgrad).
+// MFMA engine, all five columns of a 32-point tile in one workgroup: pde_jet.hip / pde_jet6.hip), the
+// backward is the hand-written reverse of that tangent program (the four tangent adjoints feed their
+// second-derivative corrections into the value adjoint in registers), fused by default with the hidden
+// layers' weight gradients (pde_fuse.hip); the remaining weight gradients are split-K MFMA over the
+// stashed tiles (launch_pde_wgrad below).  This unit holds the prefilter, the residuals and the host side.
 // Points are bucketed by RK2 step count so workgroups of the prefilter are homogeneous.
 #include <stdlib.h>
 #include "common.h"
@@ -279,7 +281,7 @@ struct PdePlan {
     float4* xw16; uint8_t* near; int* blist; int* bcount; void* img16; void* img16lo;   // fp16 pre-pass (pre16.hip)
     void* x6img;                                                                       // x6 prefilter (vel_x6.hip)
     double* sums; unsigned long long* lb; int64_t zero_bytes;
-    float *vel_frag, *a_frag, *vel_x4, *a_x4, *stash, *seeds, *wout, *slabs;
+    float *vel_frag, *a_frag, *vel_x4f, *vel_x4b, *a_x4b, *stash, *seeds, *wout, *slabs;
     int64_t chunk, total;
 };
 static void plan_pde(int64_t P, void* ws, PdePlan* L) {
@@ -305,8 +307,8 @@ static void plan_pde(int64_t P, void* ws, PdePlan* L) {
     L->x6img = B.take<float4>(X6_IMAGE_BYTES / 16);
     L->dcount = B.take<int>(16);
     L->vel_frag = B.take<float>(VEL_FRAG_FLOATS); L->a_frag = B.take<float>(VEL_FRAG_FLOATS);
-    L->vel_x4 = B.take<float>(VEL_X4_FLOATS);
-    L->a_x4 = B.take<float>(4 * X4_FLOATS(4, 64) + X4_FLOATS(4, 4));      // transposed fragments of a_weight_net (pde_fuse.hip)
+    L->vel_x4f = B.take<float>(VEL_X4F_FLOATS); L->vel_x4b = B.take<float>(VEL_X4B_FLOATS);      // (with T0, which no PDE kernel reads: the set travels whole)
+    L->a_x4b = B.take<float>(A_X4B_FLOATS);                                                      // transposed fragments of a_weight_net (pde_fuse.hip)
     L->chunk = P < PDE_CHUNK ? (P + WG_SAMPLES - 1) / WG_SAMPLES * WG_SAMPLES : PDE_CHUNK;
     L->stash = B.take<float>(L->chunk / TILE * (int64_t)PDE_TILE_ROWS * REGF);
     L->seeds = B.take<float>(36 * L->chunk);
@@ -367,15 +369,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     if (L.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld bytes, got %lld", (long long)L.total, (long long)workspace_bytes);
     if (launch_zero(L.cls_count, L.zero_bytes, st)) return 1;     // histogram / counts, loss sums, look-back words: one fill (a kernel, not hipMemsetAsync: common.h)
     const bool fl = sw(NVFI_FUSED_LAUNCH) != 0;
-    PackJobs jobs; jobs.n = 0;
-    VelFrags VW, AW;
-    FragCache FC; const bool cached = f->frags != nullptr;       // round 5: the field's fragment cache (nvfi_pack_frags) instead of a repack per call
-    if (cached) frag_cache_layout(f->frags, &FC);
-    if (pack_vel_frags(f->vW, f->vb, cached ? FC.vel : L.vel_frag, &VW, &jobs)) return 3;
-    if (pack_vel_frags(f->aW, f->ab, cached ? FC.anet : L.a_frag, &AW, &jobs)) return 3;
-    if (!cached && launch_pack(jobs, st)) return 1;
-    // fused jet kernels (pde_jet.hip / pde_jet6.hip): x4 copies of the v-net fragments.  (The column-parallel Jacobian kernels of round 1 - one workgroup
-    // per (tile, column), NVFI_PDE_JET=0 - were retired in round 6.)
+    // fused jet kernels (pde_jet.hip / pde_jet6.hip): they read x4 copies of the v-net fragments
     // NVFI_PDE_FUSE (default 1): pde_fuse.hip - weight_net's Jacobian adjoint and its four 128 x 128 weight gradients in one persistent kernel
     // (no gz_1..gz_4 stash, no second pass over the z / zd stash); 0: k_pde_jet_bwd + k_wgrad_ring8 over the full adjoint stash
     const int pde_fuse = sw(NVFI_PDE_FUSE);
@@ -389,36 +383,12 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     const int pre16 = sw(NVFI_PDE_PREFILTER);
     if (pre16 == PRE_UNKNOWN) return nvfi_fail(2, "NVFI_PDE_PREFILTER must be fp32, x6, fp16band or split16band");
     const float band16 = pre16 == PRE_SPLIT16BAND ? 1e-3f : 0.1f, eps16 = pre16 == PRE_SPLIT16BAND ? 2e-5f : 2e-3f;
-    const float4* f4[6] = {nullptr}; const float4* t4[6] = {nullptr};
-    if (cached) { x4f_pointers(FC.vel_x4f, f4); x4b_pointers(FC.vel_x4b, t4); }
-    else {
-        X4Jobs xj; xj.n = 0;
-        float* p = L.vel_x4;
-        auto add = [&](const float* src, int MT, int NS, const float4** slot) {
-            xj.src[xj.n] = src; xj.dst[xj.n] = p; xj.MT[xj.n] = MT; xj.NS[xj.n] = NS; ++xj.n;
-            *slot = reinterpret_cast<const float4*>(p);
-            p += X4_FLOATS(MT, NS);
-        };
-        add(VW.f[0], 4, 14, &f4[0]);
-        for (int l = 1; l <= 4; ++l) add(VW.f[l], 4, 64, &f4[l]);
-        add(VW.f[5], 1, 64, &f4[5]);
-        for (int l = 1; l <= 4; ++l) add(VW.t[l], 4, 64, &t4[l]);
-        add(VW.t[5], 4, 4, &t4[5]);
-        if (launch_frag_x4(xj, st)) return 1;
-    }
-    const float4* ta4[6] = {nullptr};
-    if (cached) a_x4b_pointers(FC.a_x4b, ta4);
-    else if (pde_fuse && grads) {
-        X4Jobs xj; xj.n = 0;
-        float* p = L.a_x4;
-        for (int l = 1; l <= 5; ++l) {
-            const int NS = l < 5 ? 64 : 4;
-            xj.src[xj.n] = AW.t[l]; xj.dst[xj.n] = p; xj.MT[xj.n] = 4; xj.NS[xj.n] = NS; ++xj.n;
-            ta4[l] = reinterpret_cast<const float4*>(p);
-            p += X4_FLOATS(4, NS);
-        }
-        if (launch_frag_x4(xj, st)) return 1;
-    }
+    // the velocity net's images (frags.h): the cache's, or packed here - one k_pack, one k_frag_x4 per net, one x6 pack
+    const bool jet_x6 = sw(NVFI_PDE_JET_X6) != 0;
+    const unsigned need = VI_VEL | VI_ANET | VI_X4F | VI_X4B | ((pde_fuse && grads) ? VI_A_X4B : 0) | ((pre16 == PRE_X6 || jet_x6) ? VI_X6 : 0);
+    VelImages VI;
+    if (int rc = vel_images(f, need, VelImageRoom{L.vel_frag, L.a_frag, L.vel_x4f, L.vel_x4b, L.a_x4b, L.x6img, nullptr}, &VI, nullptr, 0, st)) return rc;
+    const VelFrags &VW = VI.VW, &AW = VI.AW;
     const unsigned pb = (unsigned)((P + 255) / 256);
     PdePrepArgs pa; pa.f = *f; pa.P = P; pa.points = points; pa.t = t; pa.qorig = L.qorig; pa.xw = L.xw; pa.pt_t = L.pt_t; pa.pt_base = L.pt_base;
     pa.cls = L.cls; pa.rank = L.rank; pa.cls_count = L.cls_count;
@@ -433,7 +403,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
     da.f = *f; da.per_point_t = 1; da.sigma_out = L.sig;
     SplitArgs sa; memset(&sa, 0, sizeof(sa));
     sa.f = *f; sa.xw = L.xw; sa.dt_max = ra.dt_max; sa.max_steps = PDE_MAX_CLASS;
-    for (int l = 0; l < 6; ++l) { sa.f4[l] = f4[l]; sa.bv[l] = VW.b[l]; }
+    for (int l = 0; l < 6; ++l) { sa.f4[l] = VI.f4[l]; sa.bv[l] = VW.b[l]; }
     if (pre16 == PRE_FP32) {
         sa.count = nullptr; sa.n_direct = P; sa.list = L.perm; sa.pt_t = L.pt_t_perm; sa.pt_base = L.pt_base_perm;
         if (launch_rk2_split(sa, P, st)) return 1;
@@ -441,9 +411,8 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
         if (launch_density_q(da, P, st)) return 1;
     } else if (pre16 == PRE_X6) {
         X6Args xa; memset(&xa, 0, sizeof(xa));
-        xa.f = *f; xa.img = cached ? FC.vel_x6 : L.x6img; xa.n_direct = P; xa.list = L.perm; xa.xw = L.xw; xa.pt_t = L.pt_t_perm; xa.pt_base = L.pt_base_perm;
+        xa.f = *f; xa.img = VI.x6; xa.n_direct = P; xa.list = L.perm; xa.xw = L.xw; xa.pt_t = L.pt_t_perm; xa.pt_base = L.pt_base_perm;
         xa.dt_max = ra.dt_max; xa.max_steps = PDE_MAX_CLASS;
-        if (!cached && launch_pack_x6(f->vW, L.x6img, st)) return 1;
         { ProfScope ps(PK_PDE_PREFILTER, st); if (launch_rk2_x6(xa, P, st)) return 1; }
         da.n_direct = P; da.xw = L.xw;
         if (launch_density_q(da, P, st)) return 1;
@@ -501,7 +470,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
         const unsigned wgs = (unsigned)(cap / WG_SAMPLES);
         ja.wgs = (int)wgs;
         ja.wout = L.wout;
-        for (int l = 0; l < 6; ++l) { ja.f4[l] = f4[l]; ja.t4[l] = t4[l]; ja.bv[l] = VW.b[l]; }
+        for (int l = 0; l < 6; ++l) { ja.f4[l] = VI.f4[l]; ja.t4[l] = VI.t4[l]; ja.bv[l] = VW.b[l]; }
         // the fused adjoint is the only reader of the hidden layers' pre-activations: they travel as x4 stash blocks (row-major for the unfused adjoint)
         const bool fuse_ok = pde_fuse && grads && grads->vW[1] && grads->vW[2] && grads->vW[3] && grads->vW[4];
         ja.x4 = fuse_ok ? 1 : 0;
@@ -511,9 +480,8 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
                 // all five weight_net columns of a tile in one workgroup; the ReLU acceleration net keeps its column kernel
                 // (the launch carries the acceleration net's value column as trailing workgroups: they fill the tail of the jet tiles)
                 // NVFI_PDE_JET_X6 (default 1, round 6): pde_jet6.hip - the same program with the hidden layers' products on the 16-bit matrix pipe
-                if (sw(NVFI_PDE_JET_X6)) {
-                    if (!cached && pre16 != PRE_X6 && first == 0 && launch_pack_x6(f->vW, L.x6img, st)) return 1;      // (the x6 prefilter has packed it already)
-                    if (launch_pde_jet6_fwd(ja, cached ? FC.vel_x6 : L.x6img, (unsigned)(cap / TILE), wgs, st)) return 1;
+                if (jet_x6) {
+                    if (launch_pde_jet6_fwd(ja, VI.x6, (unsigned)(cap / TILE), wgs, st)) return 1;
                 } else if (launch_pde_jet_fwd(ja, (unsigned)(cap / TILE), wgs, st)) return 1;
             }
             if (fl) {
@@ -550,7 +518,7 @@ static int pde_loss_impl(const nvfi_field_desc* f, int64_t P, const float* point
                     // pde_fuse.hip: the adjoint of weight_net's five columns AND its four hidden-layer weight gradients in one persistent kernel;
                     // the acceleration net's adjoint keeps k_pde_jet_bwd's trailing workgroups (a launch with zero jet tiles)
                     PdeFuseArgs fa; memset(&fa, 0, sizeof(fa));
-                    for (int l = 0; l < 6; ++l) { fa.t4[l] = t4[l]; fa.ta4[l] = ta4[l]; }
+                    for (int l = 0; l < 6; ++l) { fa.t4[l] = VI.t4[l]; fa.ta4[l] = VI.ta4[l]; }
                     fa.kcount = L.kcount; fa.first = first; fa.cap = cap; fa.stash = L.stash; fa.seeds = L.seeds; fa.x4 = ja.x4;
                     fa.slabs = fused_slabs; fa.layer_stride = (int64_t)PDE_NSLAB * (128 * 128 + 128); fa.slab_floats = 128 * 128 + 128;
                     // ... and, when all four hidden-layer gradients of a_weight_net are wanted, its adjoint + those gradients as the kernel's second

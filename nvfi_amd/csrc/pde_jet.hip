@@ -16,8 +16,11 @@
 //     weight-gradient kernel needs (z, zd_j, gz, gzd_j): 4016 rows per tile instead of 5296.
 //   * the 128 -> 6 output layer is split over the waves along K (each wave contracts its own 32 rows) and summed through LDS.
 //
-// The arithmetic per element is the one of pde.hip (same formulas, same MFMA accumulation order), so both paths agree to rounding of
-// the split-K output layer; pde.hip's column kernels remain for the ReLU acceleration net and as NVFI_PDE_JET=0.
+// The column-parallel kernels this replaced (one workgroup per tile and column, pde.hip in rounds 1-5) were retired in round 6.  The ReLU
+// acceleration net, whose Jacobian is not taken, rides as trailing workgroups of the same launches (value column forward,
+// velnet_value_backward of pde.h in the adjoint); pde_jet6.hip is this forward with the hidden layers on the 16-bit matrix pipe, and
+// pde_fuse.hip the adjoint fused with the hidden layers' weight gradients.  k_frag_x4 below makes the x4 weight copies of an uncached
+// call from its plain fragments (the jobs are vel_images', frags.hip).
 #include <stdio.h>
 #include <stdlib.h>
 #include "common.h"
@@ -42,34 +45,6 @@ int launch_frag_x4(const X4Jobs& jobs, hipStream_t st) {
     hipLaunchKernelGGL(k_frag_x4, dim3(jobs.n, 16), dim3(256), 0, st, jobs);
     LAUNCHCK();
     return 0;
-}
-
-int pack_vel_x4_fwd(const VelFrags& W, float* buf, const float4** f4, hipStream_t st) {
-    X4Jobs xj; xj.n = 0;
-    float* p = buf;
-    auto add = [&](const float* src, int MT, int NS, const float4** slot) {
-        xj.src[xj.n] = src; xj.dst[xj.n] = p; xj.MT[xj.n] = MT; xj.NS[xj.n] = NS; ++xj.n;
-        *slot = reinterpret_cast<const float4*>(p);
-        p += X4_FLOATS(MT, NS);
-    };
-    add(W.f[0], 4, 14, &f4[0]);
-    for (int l = 1; l <= 4; ++l) add(W.f[l], 4, 64, &f4[l]);
-    add(W.f[5], 1, 64, &f4[5]);
-    return launch_frag_x4(xj, st);
-}
-
-int pack_vel_x4_bwd(const VelFrags& W, float* buf, const float4** t4, hipStream_t st) {
-    X4Jobs xj; xj.n = 0;
-    float* p = buf;
-    auto add = [&](const float* src, int MT, int NS, const float4** slot) {
-        xj.src[xj.n] = src; xj.dst[xj.n] = p; xj.MT[xj.n] = MT; xj.NS[xj.n] = NS; ++xj.n;
-        *slot = reinterpret_cast<const float4*>(p);
-        p += X4_FLOATS(MT, NS);
-    };
-    add(W.t[0], 1, 64, &t4[0]);
-    for (int l = 1; l <= 4; ++l) add(W.t[l], 4, 64, &t4[l]);
-    add(W.t[5], 4, 4, &t4[5]);
-    return launch_frag_x4(xj, st);
 }
 
 #define JET_NC 5
@@ -278,7 +253,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_pde_jet_bwd(PdeJetArgs a) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) s6[k] = i < (int)a.cap ? a.seeds[(size_t)(30 + k) * a.cap + i] : 0.f;
         scatter6(s6, h, r4);
-        velnet_value_backward<0, false>(a.Wa, lds, lds + LDS_W_FLOATS, lane, r4, T + PDE_ZA * REGF, nullptr, T + PDE_GAA * REGF);
+        velnet_value_backward<0>(a.Wa, lds, lds + LDS_W_FLOATS, lane, r4, T + PDE_ZA * REGF, T + PDE_GAA * REGF);
         return;
     }
     const int tile = blockIdx.x;

@@ -13,10 +13,9 @@
 #include "frags.h"
 #include "x6.h"
 
-// the training warp's kernel family and what it means for the stash layout (forward and backward must agree, so both ask here):
-// NVFI_RK2_X6 (default 1): the x6 kernels; NVFI_RK2_FUSE (default 1): the adjoint + hidden-layer weight gradients in one persistent kernel - then the z
-// rows of layers 0..3 have ONE reader and travel as x4 stash blocks (a quarter of the stash instructions on both sides; NVFI_RK2_X4=0: row-major)
-static bool warp_stash_x4(const nvfi_field_desc* f) { return sw(NVFI_RK2_X4) && sw(NVFI_RK2_X6) && sw(NVFI_RK2_FUSE) && !(f->vel_fp16 & 4); }
+// The warp's kernel family (warp_kind) and what it means for the training stash (warp_stash_x4) are frags.h's: NVFI_RK2_X6 (default 1): the x6
+// kernels; NVFI_RK2_FUSE (default 1): the adjoint + hidden-layer weight gradients in one persistent kernel - then the z rows of layers 0..3 have
+// ONE reader and travel as x4 stash blocks (a quarter of the stash instructions on both sides; NVFI_RK2_X4=0: row-major)
 
 // Optional side stream for the plane-gradient scatters (NVFI_SIDE_STREAM=1): they are bound by L2 atomics and leave the MFMA
 // pipes idle, so the backward can fork them next to the weight-gradient / RK2-adjoint kernels and join before returning.
@@ -117,7 +116,7 @@ static void plan_render(const nvfi_field_desc* f, int64_t R, int flags, int nste
     P->xpre = B.take<float>(N);
     P->vel_frag = B.take<float>(VEL_FRAG_FLOATS);
     P->vel_x4 = nsteps > 0 ? B.take<float>(VEL_X4F_FLOATS) : nullptr;
-    P->img16 = (nsteps > 0 && ((!train && (f->vel_fp16 & 3)) || (train && (f->vel_fp16 & 4)))) ? (void*)B.take<float4>(2 * PRE16_IMAGE_BYTES / 16) : nullptr;   // fp16 images (hi, lo)
+    P->img16 = (nsteps > 0 && warp_fp16_room(f, train)) ? (void*)B.take<float4>(2 * PRE16_IMAGE_BYTES / 16) : nullptr;   // fp16 images (hi, lo)
     P->vel_x4b = (nsteps > 0 && train) ? B.take<float>(VEL_X4B_FLOATS) : nullptr;
     P->x6img = nsteps > 0 ? (void*)B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;      // the x6 images when the descriptor carries no fragment cache
     P->x6imgT = (nsteps > 0 && train) ? (void*)B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;      // ... and their transposes (the adjoint's dgrad, vel_fuse.hip)
@@ -216,13 +215,13 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
     if (launch_ray_head(sc, R, rays_o, P.counters, P.zero_bytes, P.counters + 2, fl, st)) return 1;
     // fragments (weights change every optimiser step: repack per call, ~0.3 MB)
     // (round 5: or not at all - a descriptor that carries the field's fragment cache, nvfi_pack_frags, points the kernels at it)
+    // the velocity net's images of the warp's kernel come from vel_images (frags.h); the render MLP's pack jobs ride in its k_pack launch
     PackJobs jobs; jobs.n = 0;
-    VelFrags VW; RenderFrags RW;
-    FragCache FC; const bool cached = f->frags != nullptr;
-    if (cached) frag_cache_layout(f->frags, &FC);
-    if (f->use_vel && nsteps > 0) { if (pack_vel_frags(f->vW, f->vb, cached ? FC.vel : P.vel_frag, &VW, &jobs)) return 3; }
-    if (pack_render_frags(f, cached ? FC.render : P.render_frag, &RW, &jobs)) return 3;
-    if (!cached && launch_pack(jobs, st)) return 1;
+    RenderFrags RW; VelImages VI;
+    if (pack_render_frags(f, render_frag_room(f, P.render_frag), &RW, &jobs)) return 3;
+    const WarpKind kind = warp_kind(f, train, false);
+    const unsigned need = nsteps > 0 ? (VI_VEL | (kind == WARP_X6 ? VI_X6 : (kind == WARP_FP32 ? VI_X4F : 0))) : 0;
+    if (int rc = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, P.x6imgT}, &VI, &jobs, 0, st)) return rc;
     // sampling; second compact list (nsteps > 0): the valid samples inside the velocity gate (counters[3])
     SampleArgs sa; memset(&sa, 0, sizeof(sa));
     sa.f = *f; sa.R = R; sa.o = rays_o; sa.d = rays_d; sa.u = jitter; sa.train = train; sa.inside = P.counters + 2;
@@ -232,7 +231,7 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
     // velocity warp back to the keyframe
     if (nsteps > 0) {
         Rk2Args ra; memset(&ra, 0, sizeof(ra));
-        ra.f = *f; ra.Wv = VW; ra.count = P.counters + 3; ra.list = P.rlist; ra.xw = P.xw; ra.xout = nullptr;
+        ra.f = *f; ra.Wv = VI.VW; ra.count = P.counters + 3; ra.list = P.rlist; ra.xw = P.xw; ra.xout = nullptr;
         ra.nsteps = nsteps; ra.sched = sched;
         for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
         ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles;
@@ -240,13 +239,11 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
         // numbers bit for bit - was retired in round 6)
         // round 5: the warp on the x6 evaluation (vel_x6.hip: the hidden layers' fp32 products formed exactly from three bfloat16 terms per operand
         // on the 16-bit matrix pipe; same stash / records for the fp32 adjoint) unless NVFI_RK2_X6=0 or an fp16-input mode is asked for
-        const int vf = f->vel_fp16 & 3;
-        if ((sw(NVFI_RK2_X6) && !(train && (f->vel_fp16 & 4)) && (train || vf == 0 || vf == 3)) || (!train && vf == 3)) {
+        if (kind == WARP_X6) {
             ra.z_x4 = (train && warp_stash_x4(f)) ? 1 : 0;
-            X6UniArgs xa; xa.r = ra; xa.img = cached ? FC.vel_x6 : P.x6img;
-            if (!cached && launch_pack_x6(f->vW, P.x6img, st)) return 1;
+            X6UniArgs xa; xa.r = ra; xa.img = VI.x6;
             if (launch_rk2_x6_uni(xa, N, train, st)) return 1;
-        } else if (((f->vel_fp16 & 3) && !train) || ((f->vel_fp16 & 4) && train)) {
+        } else if (kind == WARP_FP16IN) {
             // opt-in fp16-input modes (pre16.hip): eval-mode renders (bits 0-1), and - bit 2 - the FORWARD of a training render's warp, which
             // writes the same stash as k_rk2_split_uni<STASH> (the adjoint and the weight gradients stay fp32 MFMA)
             Rk16Args h; memset(&h, 0, sizeof(h));
@@ -256,9 +253,7 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
             if (launch_rk2_inf16(f, h, true, st, train)) return 1;
         } else {
             SplitUniArgs ua; ua.r = ra;
-            if (cached) x4f_pointers(FC.vel_x4f, ua.f4);
-            else if (pack_vel_x4_fwd(VW, P.vel_x4, ua.f4, st)) return 1;
-            for (int l = 0; l < 6; ++l) ua.bv[l] = VW.b[l];
+            for (int l = 0; l < 6; ++l) { ua.f4[l] = VI.f4[l]; ua.bv[l] = VI.VW.b[l]; }
             if (launch_rk2_split_uni(ua, N, train, st)) return 1;
         }
     }
@@ -393,13 +388,14 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
             if (gdet.apt[i]) gdet.apt[i] = reinterpret_cast<float*>(P.shadow + det_off[9 + i]);
         }
     }
-    // fragments were packed by the forward into the same workspace
-    VelFrags VW; RenderFrags RW; PackJobs dummy; dummy.n = 0;
-    FragCache FC; const bool cached = f->frags != nullptr;      // (... or live in the field's fragment cache: the same weights, the caller's contract)
-    if (cached) frag_cache_layout(f->frags, &FC);
-    if (f->use_vel && nsteps > 0) pack_vel_frags(f->vW, f->vb, cached ? FC.vel : P.vel_frag, &VW, &dummy);
-    dummy.n = 0;
-    pack_render_frags(f, cached ? FC.render : P.render_frag, &RW, &dummy);
+    // the plain fragments were packed by the forward into the same workspace (... or live in the field's fragment cache: the same weights, the
+    // caller's contract); the adjoint's own images - x4 transposed copies, and the transposed x6 image of the fused kernel - are packed here
+    RenderFrags RW; PackJobs unused; unused.n = 0;
+    pack_render_frags(f, render_frag_room(f, P.render_frag), &RW, &unused);
+    const int fuse = sw(NVFI_RK2_FUSE) ? 1 : 0;
+    VelImages VI;
+    if (int rc = vel_images(f, nsteps > 0 ? (VI_VEL | VI_X4B | (fuse ? VI_X6T : 0)) : 0, VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, P.x6imgT},
+                            &VI, nullptr, VI_VEL, st)) return rc;
     bool forked = false;
     // appearance branch
     AppArgs aa; memset(&aa, 0, sizeof(aa));
@@ -497,30 +493,24 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
     // RK2 adjoint + velocity-net weight gradients
     if (nsteps > 0) {
         Rk2Args ra; memset(&ra, 0, sizeof(ra));
-        ra.f = *f; ra.Wv = VW; ra.count = P.counters + 3; ra.list = P.rlist; ra.xw = P.xw;
+        ra.f = *f; ra.Wv = VI.VW; ra.count = P.counters + 3; ra.list = P.rlist; ra.xw = P.xw;
         ra.nsteps = nsteps; ra.sched = sched;
         for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
         ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles; ra.gxk = P.gxk;
         // NVFI_RK2_FUSE (default 1): vel_fuse.hip - the adjoint AND the four 128 x 128 weight gradients in one persistent kernel (no g_1..g_4
         // stash, no second pass over the z stash); 0: k_rk2_split_bwd + k_wgrad_ring8 over the full adjoint stash
-        const int fuse = sw(NVFI_RK2_FUSE) ? 1 : 0;
-        ra.z_x4 = warp_stash_x4(f) ? 1 : 0;                              // (what the forward wrote: the same predicate)
+        ra.z_x4 = warp_stash_x4(f) ? 1 : 0;                              // (what the forward wrote)
         float* vslabs = (fork2 || merge_wgrad) ? P.slabs2 : P.slabs;      // (merged launches: the render MLP's slabs in P.slabs are still live)
         int fused_nslab = 0;
         if (fuse) {
             FuseBwdArgs fa; memset(&fa, 0, sizeof(fa));
             fa.r = ra; fa.slabs = vslabs; fa.layer_stride = (int64_t)NSLAB * SLAB_FLOATS; fa.slab_floats = SLAB_FLOATS;
-            if (cached) { x4b_pointers(FC.vel_x4b, fa.t4); fa.imgT = FC.vel_x6t; }
-            else {
-                if (pack_vel_x4_bwd(VW, P.vel_x4b, fa.t4, st)) return 1;
-                if (launch_pack_x6(f->vW, P.x6img, st, P.x6imgT)) return 1;
-                fa.imgT = P.x6imgT;
-            }
+            for (int l = 0; l < 6; ++l) fa.t4[l] = VI.t4[l];
+            fa.imgT = VI.x6t;
             if (launch_rk2_fuse_bwd(fa, N, NSLAB, &fused_nslab, st)) return 1;
         } else {              // vel_split.hip (k_rk2_bwd of vel.hip, NVFI_RK2_SPLIT_BWD=0 - the same adjoint stash bit for bit - was retired in round 6)
             SplitBwdArgs ba; ba.r = ra;
-            if (cached) x4b_pointers(FC.vel_x4b, ba.t4);
-            else if (pack_vel_x4_bwd(VW, P.vel_x4b, ba.t4, st)) return 1;
+            for (int l = 0; l < 6; ++l) ba.t4[l] = VI.t4[l];
             if (launch_rk2_split_bwd(ba, N, st)) return 1;
         }
         if (launch_vel_wgrad(P.zst, P.x0st, P.gst, P.counters + 3, (int)P.cap_tiles, 2 * nsteps, BM_SILU, vslabs, NSLAB,

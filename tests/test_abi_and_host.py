@@ -355,3 +355,36 @@ def test_render_workspace_layout_is_pinned():
     from nvfi_amd import _lib
     assert rc == 2 and b"RK2 steps" in _lib.lib().nvfi_last_error()
     assert _plan_bytes(d, 8, 0, d.tmax + 63.5 * dtm)[0] == 0
+
+
+# bytes of the point calls' workspaces and of the fragment cache in the library of the commit before vel_images() (frags.h) became the one
+# way to the velocity net's weight images, for N / P = 1, 255, 256, 4096, 262144, 262145
+POINT_SIZES = (1, 255, 256, 4096, 262144, 262145)
+POINT_BYTES = {
+    "nvfi_pde_workspace_bytes": (311206912, 315375360, 315375360, 440198656, 8828347392, 8828351488),
+    "nvfi_vel_workspace_bytes": (1161472, 1168384, 1168384, 1275904, 8501248, 8501504),
+    "nvfi_alpha_workspace_bytes": (997120, 1003520, 1003520, 1111040, 8336384, 8337152),
+    "nvfi_char_workspace_bytes": (1162496, 1173760, 1173760, 1358080, 13744384, 13745408),
+}
+FRAG_CACHE_BYTES = 3125504
+X4_T0_BYTES = 1 * (64 // 4) * 256 * 4      # the x4 copy of weight_net's transposed input layer: 1 tile x 64 K steps (pde.h: X4_FLOATS(1, 64))
+
+
+def test_point_workspace_sizes_are_pinned():
+    """The published workspace sizes of the PDE term, nvfi_vel_eval / nvfi_integrate_pos, nvfi_compute_alpha and the characteristic loss, and the
+    size of the fragment cache, for golden field A's sizes are literals of the parent library.  One moved on purpose: an uncached PDE call packs
+    weight_net's whole transposed x4 set - T0 travels with it, although no PDE kernel reads it - so its workspace is 16 KB larger at every P."""
+    import ctypes as C
+    from nvfi_amd import _lib
+    d = _plan_desc()
+    assert X4_T0_BYTES == 16384
+    for name, want in POINT_BYTES.items():
+        got = []
+        for n in POINT_SIZES:
+            nb = C.c_int64(-1)
+            assert getattr(_lib.lib(), name)(C.byref(d), C.c_int64(n), C.byref(nb)) == 0, name
+            got.append(nb.value)
+        grow = X4_T0_BYTES if name == "nvfi_pde_workspace_bytes" else 0
+        assert tuple(got) == tuple(w + grow for w in want), name
+    nb = C.c_int64(-1)
+    assert _lib.lib().nvfi_frag_cache_bytes(C.byref(d), C.byref(nb)) == 0 and nb.value == FRAG_CACHE_BYTES
