@@ -345,6 +345,25 @@ int nvfi_vel_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes
 /* integrate_pos (tensorf_keyframe.py:575-611): x (N,3) normalised, t (N), base (N) -> xk (N,3) */
 int nvfi_integrate_pos(const nvfi_field_desc* f, int64_t N, const float* x, const float* t, const float* base,
                        float* xk, void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- differentiable advection (an addition to ABI v5; csrc/advect.hip): the adjoint of xk = integrate_pos(x, t, t_target) for HOST scalar times,
+ *      as autograd carries it through the reference's plain torch code (tensorf_keyframe.py:575-611): RK2 midpoint steps of at most ts / 2, the
+ *      last one taking the remainder, the gate of VelocityAABB[Sur] tested on the current point and on the midpoint, with the surround box a step
+ *      that leaves it rejected - every such decision held fixed.  The forward is nvfi_integrate_pos (t and base filled with the two scalars) and
+ *      keeps nothing: this call runs the warp again on the uniform schedule in training form, then the render's unfused adjoint and its weight-
+ *      gradient jobs on that stash.
+ *        g_x (N,3), WRITTEN (may be NULL): d loss / d x for the upstream g_xk = d loss / d xk.  A point gated at both evaluations of a step passes its
+ *        gradient through that step unchanged; a rejected step is the identity.
+ *        grads->vW / vb: the gradient of weight_net is ACCUMULATED (a NULL member skips that tensor); no other member is read or written -
+ *        a_weight_net and the planes get nothing.
+ *      N == 0 or t == t_target: nothing is launched for the net, g_x = g_xk (a copy kernel), 0 is returned.  All launches go to `stream`; no host
+ *      synchronisation.  The workspace (caller-allocated; ~10.8 KB per point and RK2 step + 101 MB of slabs: chunk N, chunks accumulate) may be
+ *      reused by the next call on the same stream.  Errors (2): use_vel == 0, vel_fp16 modes 1 / 2, more than 64 RK2 steps (refused, not truncated);
+ *      (4): workspace too small. */
+int nvfi_advect_grad_workspace_bytes(const nvfi_field_desc* f, int64_t N, float t, float t_target, int64_t* bytes);
+int nvfi_advect_grad(const nvfi_field_desc* f, int64_t N, const float* x, float t, float t_target,
+                     const float* g_xk /* (N,3) */, float* g_x /* (N,3) or NULL, WRITTEN */,
+                     const nvfi_grads* grads /* vW / vb ACCUMULATED, the rest ignored */,
+                     void* workspace, int64_t workspace_bytes, void* stream);
 /* compute_densityfeature + feature2density (tensorf_keyframe.py:233-272, 312-321): xyzt (N,4) -> feat (N), sigma (N) */
 int nvfi_density_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, float* feat, float* sigma, void* stream);
 /* compute_appfeature + MLPRender_PE (tensorf_keyframe.py:274-310, tensorf_base.py:88-98): xyzt (N,4), view (N,3) -> rgb (N,3) */

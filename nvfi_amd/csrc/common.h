@@ -140,13 +140,10 @@ __host__ __device__ inline float dt_max_of(const nvfi_field_desc& f) {
     return f.K > 1 ? (float)(0.5 * (double)f.tmax / (double)(f.K - 1)) : 1.f;
 }
 
-// number of RK2 steps back to the keyframe time and their (dt, start time) sequence for a per-call scalar t (tensorf_keyframe.py:575-609);
-// -1: more than MAX_RK_STEPS.  The ONE copy of the loop: the host plans with it, k_sched / k_prologue (render_rays.hip) replay it on the device
-__host__ __device__ inline int rk_schedule(const nvfi_field_desc& f, float t, int flags, float* base_out, float* dts, float* tcs) {
-    float base = (flags & NVFI_TRANSFER) ? 0.f : snap_base(f, t);
-    *base_out = base;
-    if (!f.use_vel || is_close(t, base)) return 0;
-    float dtm = dt_max_of(f), off = t - base, tc = t;
+// the ONE copy of integrate_pos' step loop (tensorf_keyframe.py:575-609): RK2 steps of at most dtm from t to `target`, the last one taking the
+// remainder; their (dt, start time) sequence and their number, -1: more than MAX_RK_STEPS.  flow64.schedule (tests) is its float restatement
+__host__ __device__ inline int rk_steps(float dtm, float t, float target, float* dts, float* tcs) {
+    float off = t - target, tc = t;
     int n = 0;
     while (fabsf(off) > 0.f) {
         if (n >= MAX_RK_STEPS) return -1;
@@ -157,6 +154,18 @@ __host__ __device__ inline int rk_schedule(const nvfi_field_desc& f, float t, in
         ++n;
     }
     return n;
+}
+// number of RK2 steps back to the keyframe time and their (dt, start time) sequence for a per-call scalar t; -1: more than MAX_RK_STEPS.
+// The host plans with it, k_sched / k_prologue (render_rays.hip) replay it on the device
+__host__ __device__ inline int rk_schedule(const nvfi_field_desc& f, float t, int flags, float* base_out, float* dts, float* tcs) {
+    float base = (flags & NVFI_TRANSFER) ? 0.f : snap_base(f, t);
+    *base_out = base;
+    if (!f.use_vel || is_close(t, base)) return 0;
+    return rk_steps(dt_max_of(f), t, base, dts, tcs);
+}
+// the schedule from t to an explicit target time (nvfi_advect_grad, advect.hip): integrate_pos(x, t, t_target); t == t_target: no step
+__host__ __device__ inline int rk_schedule_to(const nvfi_field_desc& f, float t, float t_target, float* dts, float* tcs) {
+    return rk_steps(dt_max_of(f), t, t_target, dts, tcs);
 }
 // first row of the time planes a call at normalised time tn touches (the LDS scatter variants keep rows y0, y0 + 1 in the workgroup), for the host
 // and for sched_body.  bl_setup_xy keeps its own copy of these lines: routed through a shared helper, 13 kernels that call it change instruction order

@@ -77,8 +77,10 @@ int launch_rk2_split(const SplitArgs& a, int64_t cap_points, hipStream_t st);
 struct SplitUniArgs { Rk2Args r; const float4* f4[6]; const float* bv[6]; };
 int launch_rk2_split_uni(const SplitUniArgs& a, int64_t cap_samples, bool stash, hipStream_t st);
 // the adjoint (vel_split.hip: k_rk2_split_bwd); t4[0] = T0 (1 tile x 64 steps), t4[1..4], t4[5] (4 tiles x 4 steps)
-struct SplitBwdArgs { Rk2Args r; const float4* t4[6]; };
-int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st);
+// gx0 (behind everything the render's instantiation reads): (dense, 3) gradient with respect to the STARTING position, stored by the GX0
+// instantiation alone (want_gx0: nvfi_advect_grad, advect.hip); the render launches the plain one and leaves it NULL
+struct SplitBwdArgs { Rk2Args r; const float4* t4[6]; float* gx0 = nullptr; };
+int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st, bool want_gx0 = false);
 
 // opt-in fp16 pre-pass of the prefilter (pre16.hip)
 #define PRE16_IMAGE_BYTES 150528   // fp16 fragments of the six weight_net layers (144 KB) + fp32 biases: staged into LDS once per workgroup

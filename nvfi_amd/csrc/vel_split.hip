@@ -3,7 +3,7 @@
 //   k_rk2_split       per-point times, one 32-point tile per workgroup: the fp32 PDE prefilter and the fp32 re-evaluation list behind the
 //                     16-bit pre-passes (NVFI_PDE_PREFILTER=fp32 / the band list of pre16.hip);
 //   k_rk2_split_uni   the render warp (uniform step schedule, optional training stash), two tiles per workgroup (NVFI_RK2_X6=0);
-//   k_rk2_split_bwd   its adjoint, two tiles per workgroup (NVFI_RK2_FUSE=0).
+//   k_rk2_split_bwd   its adjoint, two tiles per workgroup (NVFI_RK2_FUSE=0); <true>: with the gradient at the starting position (nvfi_advect_grad).
 //
 // k_rk2_fwd (vel.hip) gives every wave its own tile: best throughput per staged weight byte, but a tile's latency is the whole
 // network on one SIMD (~100 k cycles per evaluation), which is what a SHORT list of points pays however few they are.  Here wave w owns
@@ -412,6 +412,9 @@ __device__ __forceinline__ void velnet_split_bwd(const float4* const* t4, float4
         for (int r = 0; r < 16; ++r) ge[t][r] = bc[(t * 16 + r) * 64 + lane];
 }
 
+// GX0 (nvfi_advect_grad): the gradient that is left in g3 after the last (= first forward) step goes to a.gx0 - the one output the render never
+// needed, its samples being constants.  The render launches the plain instantiation
+template <bool GX0>
 __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_bwd(SplitBwdArgs a) {
     constexpr int NT = SPLIT_NT;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -496,13 +499,23 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_bwd(SplitBwdArgs a)
                 for (int c = 0; c < 3; ++c) g3[t][c] = g3[t][c] + gacc[t][c] + 0.f;
             }
     }
+    if (GX0) {      // replicated state: every wave and both lane halves hold the same g3; one lane per point stores
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            if (active[t] && h == 0 && w == (t & 3)) {
+                float* o = a.gx0 + 3 * (size_t)ra.list[idx[t]];
+                o[0] = g3[t][0]; o[1] = g3[t][1]; o[2] = g3[t][2];
+            }
+    }
 }
 
-int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st) {
+int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st, bool want_gx0) {
     const int64_t tiles = (cap_samples + TILE - 1) / TILE;
     if (tiles <= 0) return 0;
     ProfScope ps(PK_RK2_BWD, st);
-    hipLaunchKernelGGL(k_rk2_split_bwd, dim3((unsigned)((tiles + SPLIT_NT - 1) / SPLIT_NT)), dim3(WG_THREADS), SPLIT_BWD_LDS_BYTES, st, a);
+    const dim3 g((unsigned)((tiles + SPLIT_NT - 1) / SPLIT_NT)), b(WG_THREADS);
+    if (want_gx0 && a.gx0) hipLaunchKernelGGL(k_rk2_split_bwd<true>, g, b, SPLIT_BWD_LDS_BYTES, st, a);
+    else hipLaunchKernelGGL(k_rk2_split_bwd<false>, g, b, SPLIT_BWD_LDS_BYTES, st, a);
     LAUNCHCK();
     return 0;
 }

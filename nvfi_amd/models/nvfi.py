@@ -51,6 +51,10 @@ class NVFi(nn.Module):
         """eval-mode render with the per-object layers of the mask field, optionally object-selected (TensorVMKeyframeTimeKplane.render_objects)"""
         return self.nvfi.render_objects(t, ray_o, ray_d, select=select, white_bg=white_bg, transfer_vel=transfer_vel)
 
+    def advect(self, pos, t, t_target, max_workspace_bytes=1 << 30):
+        """integrate_pos(pos, t, t_target) with gradients to `pos` and the velocity net (TensorVMKeyframeTimeKplane.advect)"""
+        return self.nvfi.advect(pos, t, t_target, max_workspace_bytes=max_workspace_bytes)
+
     def update_nvfi_kwargs(self, kwargs):
         """models/nvfi.py:33-35 writes every checkpoint kwarg into the field's __dict__.  Same effect here, except that the two
         entries the C-ABI descriptor caches on the host (aabb, gridSize) go through the buffer / update_stepSize."""

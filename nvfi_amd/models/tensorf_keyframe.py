@@ -408,6 +408,62 @@ class _CharFn(torch.autograd.Function):
         return (None, None, None) + tuple(out)
 
 
+class _AdvectFn(torch.autograd.Function):
+    """autograd boundary around nvfi_integrate_pos / nvfi_advect_grad (include/nvfi_hip.h) for host-scalar times.  The forward IS
+    field.integrate_pos and saves only the positions: the backward runs the warp again in training form, chunk by chunk on one workspace of at
+    most `max_ws` bytes (the stash is ~10.8 KB per point and RK2 step), and accumulates the net's gradients over the chunks."""
+
+    @staticmethod
+    def forward(ctx, field, x, t, t_target, max_ws, *params):
+        tt = torch.full((x.shape[0],), t, dtype=torch.float32, device=x.device)
+        bb = torch.full((x.shape[0],), t_target, dtype=torch.float32, device=x.device)
+        xk = field.integrate_pos(x, tt, bb)
+        ctx.field, ctx.t, ctx.t_target, ctx.max_ws = field, t, t_target, int(max_ws)
+        ctx.save_for_backward(x, *params)
+        ctx.set_materialize_grads(False)
+        return xk
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, *params = ctx.saved_tensors
+        if g is None:
+            return (None,) * (5 + len(params))
+        L = _lib.lib()
+        field = ctx.field
+        desc = field._desc(field._render_params()[:19] + list(params))
+        need = ctx.needs_input_grad[5:]
+        grads = _zero_grads(params, need)          # the plain path of _RenderFn.backward: fresh zero gradients, no arena, no side streams
+        G = field._grads_struct_vel(list(grads) + [None] * 12)
+        g = g.reshape(-1, 3).contiguous().float()
+        N = x.shape[0]
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        t, t1 = C.c_float(ctx.t), C.c_float(ctx.t_target)
+
+        def nbytes(n):
+            nb = C.c_int64(0)
+            _lib.check(L.nvfi_advect_grad_workspace_bytes(C.byref(desc), C.c_int64(n), t, t1, C.byref(nb)))
+            return nb.value
+
+        chunk = N
+        if nbytes(N) > ctx.max_ws:
+            # the plan is affine in the number of whole 128-point groups: the largest multiple of 128 that fits
+            b1, b2 = nbytes(128), nbytes(256)
+            if b1 > ctx.max_ws:
+                raise _lib.NvfiError(f"advect: max_workspace_bytes={ctx.max_ws} is below the {b1} bytes one 128-point group needs")
+            chunk = 128 * (1 + (ctx.max_ws - b1) // (b2 - b1))
+            while chunk > 128 and nbytes(chunk) > ctx.max_ws:
+                chunk -= 128
+        ws = torch.empty(nbytes(min(chunk, N)), dtype=torch.uint8, device=x.device)
+        field.last_advect_chunks = (N + chunk - 1) // chunk if N else 0
+        field.last_advect_workspace_bytes = ws.numel()
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            _lib.check(L.nvfi_advect_grad(C.byref(desc), C.c_int64(n), _lib.ptr(x[i:i + n]), t, t1, _lib.ptr(g[i:i + n]),
+                                          None if gx is None else _lib.ptr(gx[i:i + n]), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        return (None, gx, None, None, None) + tuple(grads)
+
+
 class TensorVMKeyframeTimeKplane(nn.Module):
     def __init__(self, aabb, gridSize, device, near_far, cfg):
         super().__init__()
@@ -1197,6 +1253,44 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         _lib.check(L.nvfi_integrate_pos(C.byref(desc), C.c_int64(N), _lib.ptr(x), _lib.ptr(tt), _lib.ptr(bb), _lib.ptr(out),
                                         _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
         return out
+
+    def advect(self, pos, t, t_target, max_workspace_bytes=1 << 30):
+        """integrate_pos(pos, t, t_target) for scalar times WITH gradients (tensorf_keyframe.py:575-611 under autograd): a loss on the advected
+        points reaches `pos` and the 12 tensors of vel_net.weight_net - 3-D track / scene-flow / optical-flow supervision, cycle consistency,
+        trajectory smoothness.  Every gate / rejection decision is held fixed; a_weight_net and the planes get nothing; no second-order gradients.
+        The value is integrate_pos' bit for bit.  The backward recomputes the warp in chunks whose workspace stays under `max_workspace_bytes`.
+        Under no_grad, or when neither `pos` nor a weight_net parameter requires grad, this is exactly integrate_pos (tensor times allowed).
+        More than 64 RK2 steps between the two scalar times is refused (error 2), not truncated."""
+        if not (isinstance(pos, torch.Tensor) and pos.is_cuda):
+            raise _lib.NvfiError("advect needs its points on the GPU (no CPU fallback exists)")
+        if not self.use_vel:
+            raise _lib.NvfiError("advect needs a field with a velocity net (use_vel)")
+        wparams = self._render_params()[19:31]
+        wants = torch.is_grad_enabled() and (pos.requires_grad or any(p.requires_grad for p in wparams))
+
+        def scalar(v):
+            if isinstance(v, torch.Tensor):
+                if v.numel() == 0 or bool((v != v.reshape(-1)[0]).any()):
+                    return None
+                v = v.reshape(-1)[0].item()
+            return float(np.float32(float(v)))
+
+        ts, t1s = scalar(t), scalar(t_target)
+        if ts is None or t1s is None:
+            if wants:
+                raise NotImplementedError("advect: per-point times (a tensor t / t_target with more than one distinct value) have no gradient path")
+            return self.integrate_pos(pos, t, t_target).reshape(pos.shape)
+        desc = self._desc()
+        nb = C.c_int64(0)
+        if wants and (desc.vel_fp16 & 3) in (1, 2):
+            raise NotImplementedError("advect: the fp16-input modes (vel_fp16 1 / 2) have no adjoint")
+        if (desc.vel_fp16 & 3) not in (1, 2):      # the step limit, decided on the host before anything is launched
+            _lib.check(_lib.lib().nvfi_advect_grad_workspace_bytes(C.byref(desc), C.c_int64(0), C.c_float(ts), C.c_float(t1s), C.byref(nb)))
+        x = pos.reshape(-1, 3).contiguous().float()
+        if not wants:
+            tt = torch.full((x.shape[0],), ts, dtype=torch.float32, device=x.device)
+            return self.integrate_pos(x, tt, torch.full_like(tt, t1s)).reshape(pos.shape)
+        return _AdvectFn.apply(self, x, ts, t1s, int(max_workspace_bytes), *wparams).reshape(pos.shape)
 
     @torch.no_grad()
     def compute_densityfeature(self, xyzt):
