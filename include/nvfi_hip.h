@@ -392,7 +392,9 @@ int nvfi_prof_collect(double* total_ms, int64_t* count);
 int nvfi_prof_nclasses(void);
 /* compute_alpha (tensorf_keyframe.py:508-537) for a per-call time: xyz (N,3) WORLD coordinates -> normalise, snap to the keyframe
  * (base 0 when transfer), RK2 back-advect, density, alpha = 1-exp(-sigma*length); alpha_out[n] = max(alpha_out[n], alpha) when
- * accumulate_max != 0 (getDenseAlpha's running maximum over the 60 frame times, :476-497), plain store otherwise. */
+ * accumulate_max != 0 (getDenseAlpha's running maximum over the 60 frame times, :476-497), plain store otherwise.  Like the reference's
+ * compute_alpha - and unlike the render - a time that is only isclose to its keyframe still takes its (tiny) RK2 step.  workspace_bytes below
+ * nvfi_alpha_workspace_bytes(N) is refused with error 4 before anything is launched, whichever integrator the call takes. */
 int nvfi_alpha_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes);
 int nvfi_compute_alpha(const nvfi_field_desc* f, int64_t N, const float* xyz_world, float t, int transfer, float length,
                        int accumulate_max, float* alpha_out, void* workspace, int64_t workspace_bytes, void* stream);

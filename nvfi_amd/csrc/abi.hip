@@ -151,11 +151,14 @@ extern "C" int nvfi_compute_alpha(const nvfi_field_desc* f, int64_t N, const flo
     if (N >= (1ll << 31) - 256) return nvfi_fail(2, "N too large for one call; chunk the points");
     AlphaPlan AP; plan_alpha(N, workspace, &AP);
     float* fv = AP.fv; float4* xw = AP.xw; float* sig = AP.sig;
-    if (AP.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)AP.total);
-    // the uniform step sequence back to the keyframe: the render's own schedule (0: t is a keyframe time or the field has no velocity net)
+    // the published size (nvfi_alpha_workspace_bytes) is the contract whichever integrator the call takes: refused here, before anything is launched
+    const int64_t need = AP.total + align_up(2 * N * (int64_t)sizeof(float), 256);
+    if (need > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)need);
+    // the uniform step sequence back to the keyframe (0: t IS the keyframe time or the field has no velocity net).  Not the render's rk_schedule:
+    // the reference's compute_alpha has no isclose shortcut - integrate_pos steps while t - base != 0, however small (tensorf_keyframe.py:508-537)
     Rk2Args a; memset(&a, 0, sizeof(a));
-    float base;
-    const int n = rk_schedule(*f, t, transfer ? NVFI_TRANSFER : 0, &base, a.dt, a.tcur);
+    const float base = transfer ? 0.f : snap_base(*f, t);
+    const int n = f->use_vel ? rk_steps(dt_max_of(*f), t, base, a.dt, a.tcur) : 0;
     const WarpKind kind = warp_kind(f, false, true);
     const unsigned nb = (unsigned)((N + 255) / 256);
     hipLaunchKernelGGL(k_alpha_prep, dim3(nb), dim3(256), 0, st, *f, N, xyz_world, norm_time(*f, base), xw);

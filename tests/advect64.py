@@ -56,17 +56,13 @@ def schedule(field, t, t_target):
     return steps
 
 
-def advect64(field, x, t, t_target, g, dtype=torch.float64, device="cpu"):
-    """dict: xk, gx (N, 3), the 12 gradients under their reference names (numpy, `dtype`), steps (the schedule), n_rejected (steps of points INSIDE
-    the surround box that left it and were rejected, summed over points and steps), edge (bool per point), gated_all (bool per point: outside the
-    gate at every evaluation - the point never moves and its gradient passes through unchanged), n_outside (points outside the gate at the start)"""
-    x32 = torch.as_tensor(np.asarray(x, np.float32)).reshape(-1, 3)
-    g32 = torch.as_tensor(np.asarray(g, np.float32)).reshape(-1, 3)
-    x0 = x32.to(device=device, dtype=dtype).requires_grad_(True)
-    P = {k: field.p32[k].to(device=device, dtype=dtype).requires_grad_(True) for k in NET_NAMES}
+def rk2_back(P, field, x0, steps, dtype):
+    """the ONE step loop of the float64 yardsticks that need more than the end point (advect64 below, alpha64.compute_alpha64): the steps
+    [(t_curr, d, t_mid), ...] applied to the points x0 (N, 3, `dtype`, on any device) -> the end points and dict(n_rejected, edge, gated_all,
+    n_outside) as advect64 documents them.  Differentiable where x0 / P require it."""
+    device = x0.device
     lo, hi = field.lo.to(device), field.hi.to(device)
-    steps = schedule(field, t, t_target)
-    N = x32.shape[0]
+    N = x0.shape[0]
     edge = np.zeros(N, bool)
     gated_all = torch.ones(N, dtype=torch.bool, device=device)
     cur, nrej = x0, 0
@@ -89,7 +85,20 @@ def advect64(field, x, t, t_target, g, dtype=torch.float64, device="cpu"):
             nrej += int((rej & ~outside(cur)).sum())          # (a point outside the gate never moves: not counted)
             xc = torch.where(rej[:, None], cur, xc)
         cur = xc
-    out = dict(steps=steps, n_rejected=nrej, edge=edge, gated_all=gated_all.cpu().numpy(), n_outside=n_outside)
+    return cur, dict(n_rejected=nrej, edge=edge, gated_all=gated_all.cpu().numpy(), n_outside=n_outside)
+
+
+def advect64(field, x, t, t_target, g, dtype=torch.float64, device="cpu"):
+    """dict: xk, gx (N, 3), the 12 gradients under their reference names (numpy, `dtype`), steps (the schedule), n_rejected (steps of points INSIDE
+    the surround box that left it and were rejected, summed over points and steps), edge (bool per point), gated_all (bool per point: outside the
+    gate at every evaluation - the point never moves and its gradient passes through unchanged), n_outside (points outside the gate at the start)"""
+    x32 = torch.as_tensor(np.asarray(x, np.float32)).reshape(-1, 3)
+    g32 = torch.as_tensor(np.asarray(g, np.float32)).reshape(-1, 3)
+    x0 = x32.to(device=device, dtype=dtype).requires_grad_(True)
+    P = {k: field.p32[k].to(device=device, dtype=dtype).requires_grad_(True) for k in NET_NAMES}
+    steps = schedule(field, t, t_target)
+    cur, out = rk2_back(P, field, x0, steps, dtype)
+    out["steps"] = steps
     loss = (cur * g32.to(device=device, dtype=dtype)).sum()
     grads = torch.autograd.grad(loss, [x0] + [P[k] for k in NET_NAMES], allow_unused=True)
     out["xk"] = cur.detach().cpu().numpy()

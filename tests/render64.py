@@ -30,7 +30,12 @@ given mask and the yardstick's differ are reported with their |w - thres|.
 
 Rays are independent: they are processed in chunks, and the gradients accumulate over the chunks in float64.  The loss has to be a sum over rays:
 a `Loss` (mse + w_depth mean(depth) + w_acc mean(acc^2) + sum(weight gw): the golden loss; w_depth = w_acc = 0 and no gw is the bench's mse) or a
-callable (rgb, depth, acc, weight, ray_index, R) -> per-ray terms.  AlphaGridMask.sample_alpha (eval-time culling) is NOT restated.
+callable (rgb, depth, acc, weight, ray_index, R) -> per-ray terms.
+
+Eval-time culling (tensorf_keyframe.py:656-661; AlphaGridMask.sample_alpha, tensorf_model_utils.py:433-439) is restated through `alpha_volume`:
+in an eval call (jitter None) an in-box sample stays valid only where the trilinear read of the (D, H, W) occupancy volume is > 0.  The volume is
+read at the FIELD's normalised coordinates - sample_alpha's own normalize_coord is commented out in the reference - so a mask that was built before
+shrink() is read in the new box's coordinates (tests/alpha64.py: sample_alpha64 holds the lookup and says which samples sit on a voxel boundary).
 
 Parameters are keyed by the reference's names without the `nvfi.` prefix, as helpers.named_grads gives them."""
 import numpy as np
@@ -140,8 +145,9 @@ def _planes(P, which, x4):
     for i in range(3):
         gs = x4[:, list(MAT_SPACE[i])].view(1, -1, 1, 2)
         gt = x4[:, list(MAT_TIME[i])].view(1, -1, 1, 2)
-        a = F.grid_sample(P[f"{which}_plane_space.{i}"], gs, align_corners=True).view(-1, x4.shape[0])
-        b = F.grid_sample(P[f"{which}_plane_time.{i}"], gt, align_corners=True).view(-1, x4.shape[0])
+        ps, pt = P[f"{which}_plane_space.{i}"], P[f"{which}_plane_time.{i}"]
+        a = F.grid_sample(ps, gs, align_corners=True).view(ps.shape[1], x4.shape[0])          # (the channel count is spelt out: n may be 0)
+        b = F.grid_sample(pt, gt, align_corners=True).view(pt.shape[1], x4.shape[0])
         out = a * b if out is None else out * (a * b)
     return out
 
@@ -251,12 +257,30 @@ MAP_KEYS = ("rgb", "depth", "acc", "weight", "app_mask", "own_mask", "valid", "i
 
 
 def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=None, transfer=False, grads=True, rays=None, chunk=256,
-             dtype=torch.float64, device="cpu", cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None):
+             dtype=torch.float64, device="cpu", cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None, alpha_volume=None, cull_flip=None):
     """the render of the rays `rays` (default: all; the sampling and the loss's 1 / R always refer to the full batch) -> dict of the maps (numpy),
     `loss_rays` (per-ray loss terms, float64), `loss` (their sum), `grads` {name: float64 array, or None where the parameter is not reached},
-    `flips` (indices (ray, sample) where the given app_mask differs from the yardstick's own) and `flip_dist` (their |w - thres|)"""
+    `flips` (indices (ray, sample) where the given app_mask differs from the yardstick's own) and `flip_dist` (their |w - thres|).
+    alpha_volume (D, H, W), eval calls only: the in-box samples whose occupancy read is not > 0 are culled; the result then holds `in_box` (R, S; the
+    valid map before culling), `culled`, `alpha_near` (in-box samples whose decision may fall the other way, alpha64.sample_alpha64) over ALL rays of
+    the batch; cull_flip: (n, 2) (ray, sample) whose culling decision is inverted (what a wrong lookup would do to them)"""
     smp = sample_rays(field, rays_o, rays_d, jitter)
     R = smp["o"].shape[0]
+    cull = None
+    if alpha_volume is not None and jitter is None:
+        import alpha64
+        box = smp["valid"].clone()
+        bi = box.reshape(-1).nonzero()[:, 0]
+        a, _, nr = alpha64.sample_alpha64(alpha_volume, smp["xn"].reshape(-1, 3)[bi], dtype)
+        keep = torch.zeros(box.numel(), dtype=torch.bool).index_put((bi,), torch.from_numpy(a > 0))
+        near = torch.zeros(box.numel(), dtype=torch.bool).index_put((bi,), torch.from_numpy(nr))
+        keep = keep.view(box.shape)
+        if cull_flip is not None:
+            for i, j in np.asarray(cull_flip).reshape(-1, 2):
+                assert bool(box[i, j]), "only an in-box sample has a culling decision"
+                keep[i, j] = ~keep[i, j]
+        smp["valid"] = box & keep
+        cull = dict(in_box=box.numpy(), culled=(box & ~keep).numpy(), alpha_near=near.view(box.shape).numpy())
     plan = time_plan(field, t, transfer)
     rays = np.arange(R) if rays is None else np.asarray(rays, np.int64)
     P = {k: v.detach().to(device=device, dtype=dtype, copy=True).requires_grad_(grads and loss is not None) for k, v in field.p32.items()}
@@ -279,13 +303,15 @@ def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=Non
                 outs[k].append(res[k].detach().cpu().numpy())
     out = {k: np.concatenate(v) for k, v in outs.items()}
     out["rays"], out["R"], out["plan"] = rays, R, plan
+    if cull is not None:
+        out.update(cull)
     out["loss"] = float(out["loss_rays"].sum())
     out["grads"] = {n: (g[n].cpu().numpy() if n in g else None) for n in NAMES} if (grads and loss is not None) else None
     diff = out["app_mask"] != out["own_mask"]
     out["flips"] = np.argwhere(diff)
     out["flip_dist"] = np.abs(out["weight"][diff].astype(np.float64) - field.thres)
     out["call"] = dict(field=field, rays_o=rays_o, rays_d=rays_d, t=t, jitter=jitter, white_bg=white_bg, loss=loss, transfer=transfer, chunk=chunk,
-                       dtype=dtype, device=device)
+                       dtype=dtype, device=device, alpha_volume=alpha_volume, cull_flip=cull_flip)
     return out
 
 
@@ -299,7 +325,8 @@ def with_mask(ref, app_mask):
     c = ref["call"]
     full_old = np.zeros((ref["R"], ref["app_mask"].shape[1]), bool)
     full_old[rays] = ref["app_mask"]
-    kw = dict(loss=c["loss"], transfer=c["transfer"], chunk=c["chunk"], dtype=c["dtype"], device=c["device"], rays=rays[rows])
+    kw = dict(loss=c["loss"], transfer=c["transfer"], chunk=c["chunk"], dtype=c["dtype"], device=c["device"], rays=rays[rows],
+              alpha_volume=c["alpha_volume"], cull_flip=c["cull_flip"])
     old = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], app_mask=full_old, **kw)
     new = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], app_mask=np.asarray(app_mask, bool), **kw)
     out = dict(ref)
@@ -330,7 +357,8 @@ def detach(ref, samples, branch):
     cut[torch.as_tensor(rays[samples[:, 0]]), torch.as_tensor(samples[:, 1])] = True
     mask = np.zeros((ref["R"], S), bool)
     mask[rays] = ref["app_mask"]
-    kw = dict(app_mask=mask, loss=c["loss"], transfer=c["transfer"], chunk=c["chunk"], dtype=c["dtype"], device=c["device"], rays=rays[rows])
+    kw = dict(app_mask=mask, loss=c["loss"], transfer=c["transfer"], chunk=c["chunk"], dtype=c["dtype"], device=c["device"], rays=rays[rows],
+              alpha_volume=c["alpha_volume"], cull_flip=c["cull_flip"])
     a = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], **kw)
     b = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], **kw, **{"cut_" + branch: cut})
     return {n: (None if v is None else v - a["grads"][n] + b["grads"][n]) for n, v in ref["grads"].items()}

@@ -4,7 +4,8 @@ B: this pins the yardstick that tests/test_gpu_render64.py holds the device kern
 Train cases (train_nonkey: one RK2 step, train_key: no warp, train_extrap: 2 steps on field A and 8 on field B with step rejection) with the stored
 jitter, white coin, target and per-sample weights gw: rgb, depth, acc, weight, the loss and EVERY stored gradient tensor; goldens stored empty
 (the acceleration net, and the velocity net at a keyframe) must come out absent or exactly zero.  Eval cases key, nonkey, extrap, transfer, flipbg:
-the maps.  The `amask` golden is not covered: AlphaGridMask.sample_alpha is not restated in render64.
+the maps.  The `amask` golden (the eval render through an occupancy volume, render64's `alpha_volume`) is held in tests/test_alpha64_golden.py,
+next to the rest of the occupancy path.
 
 Measured (CPU): float64 against the fp32 goldens, worst over the cases: gradients max(maxrel, rel_l2) 3.0e-6 (A:train_nonkey density_plane_time.0;
 1.2e-6 - 1.9e-6 in the other cases), loss rel err 8.4e-8, maps: no element leaves helpers.FP32_FLOOR at all (max abs err rgb 2.6e-7, acc 4.2e-7,
