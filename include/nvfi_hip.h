@@ -338,11 +338,15 @@ int nvfi_adam_step(const nvfi_adam_tensor* t, int n_tensors, float beta1, float 
 int nvfi_adam_step_dev(const nvfi_adam_tensor* t, int n_tensors, float beta1, float beta2, float eps, const float* hyper_dev, int zero_grad, void* stream);
 
 /* ---- building blocks used by train_segm-style callers and by the parity tests */
-/* VelBasis.forward (velocity_field.py:69-75): xt (N,4) -> u (N,6)=(v,a); gated!=0: VelocityAABB[Sur].forward -> (N,3) in u (stride 6) */
+/* VelBasis.forward (velocity_field.py:69-75): xt (N,4) -> u (N,6)=(v,a); gated!=0: VelocityAABB[Sur].forward -> (N,3) in u (stride 6).
+ * Errors, all before anything is launched: (2) use_vel == 0 (the field has no velocity net), component counts / n_samples the kernels are not
+ * built for; (4) a workspace under nvfi_vel_workspace_bytes(f, N). */
 int nvfi_vel_eval(const nvfi_field_desc* f, int64_t N, const float* xt, float* u6, int gated,
                   void* workspace, int64_t workspace_bytes, void* stream);
 int nvfi_vel_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes);
-/* integrate_pos (tensorf_keyframe.py:575-611): x (N,3) normalised, t (N), base (N) -> xk (N,3) */
+/* integrate_pos (tensorf_keyframe.py:575-611): x (N,3) normalised, t (N), base (N) -> xk (N,3).
+ * Errors, all before anything is launched: (2) use_vel == 0, an unsupported descriptor (as nvfi_vel_eval), N >= 2^31 - 256 (chunk the points);
+ * (4) a workspace under nvfi_vel_workspace_bytes(f, N). */
 int nvfi_integrate_pos(const nvfi_field_desc* f, int64_t N, const float* x, const float* t, const float* base,
                        float* xk, void* workspace, int64_t workspace_bytes, void* stream);
 /* ---- differentiable advection (an addition to ABI v5; csrc/advect.hip): the adjoint of xk = integrate_pos(x, t, t_target) for HOST scalar times,
@@ -364,15 +368,19 @@ int nvfi_advect_grad(const nvfi_field_desc* f, int64_t N, const float* x, float 
                      const float* g_xk /* (N,3) */, float* g_x /* (N,3) or NULL, WRITTEN */,
                      const nvfi_grads* grads /* vW / vb ACCUMULATED, the rest ignored */,
                      void* workspace, int64_t workspace_bytes, void* stream);
-/* compute_densityfeature + feature2density (tensorf_keyframe.py:233-272, 312-321): xyzt (N,4) -> feat (N), sigma (N) */
+/* compute_densityfeature + feature2density (tensorf_keyframe.py:233-272, 312-321): xyzt (N,4) -> feat (N), sigma (N).
+ * Errors (2), before anything is launched: an unsupported descriptor, N >= 2^31 - 256 (chunk the points). */
 int nvfi_density_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, float* feat, float* sigma, void* stream);
-/* compute_appfeature + MLPRender_PE (tensorf_keyframe.py:274-310, tensorf_base.py:88-98): xyzt (N,4), view (N,3) -> rgb (N,3) */
+/* compute_appfeature + MLPRender_PE (tensorf_keyframe.py:274-310, tensorf_base.py:88-98): xyzt (N,4), view (N,3) -> rgb (N,3).
+ * Errors, before anything is launched: (2) an unsupported descriptor, N >= 2^31 - 256 (chunk the points); (4) a workspace under
+ * nvfi_app_workspace_bytes(f, N). */
 int nvfi_app_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes);
 int nvfi_app_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, const float* view, float* rgb,
                 void* workspace, int64_t workspace_bytes, void* stream);
 /* renderModule(pts, viewdirs, features) as a stand-alone call - MLPRender_PE.forward (tensorf_base.py:88-98) or, with shading = 1,
  * SHRender (tensorf_model_utils.py:292-296): xyz (N,3) normalised positions, view (N,3), features (N, app_dim) -> rgb (N,3).
- * Workspace: 2 x nvfi_app_workspace_bytes(f, N) is enough.  Forward only (inside a render the module is differentiated by nvfi_render_bwd). */
+ * Workspace: 2 x nvfi_app_workspace_bytes(f, N), and less is refused (4).  Forward only (inside a render the module is differentiated by
+ * nvfi_render_bwd).  Errors (2), before anything is launched: an unsupported descriptor, N >= 2^31 - 256 (chunk the points). */
 int nvfi_render_mlp(const nvfi_field_desc* f, int64_t N, const float* xyz, const float* view, const float* features, float* rgb,
                     void* workspace, int64_t workspace_bytes, void* stream);
 /* ---- multi-GPU: rays and collocation points shard over one process per GPU; the ONLY data-path exchange is the sum of the

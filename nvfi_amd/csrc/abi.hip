@@ -56,14 +56,24 @@ extern "C" int nvfi_vel_workspace_bytes(const nvfi_field_desc* f, int64_t N, int
     *bytes = align_up((int64_t)2 * VEL_FRAG_FLOATS * 4 + 4096 + N * 16 + N * 12, 256);
     return 0;
 }
+// what both point queries of the velocity net refuse before anything is launched: a descriptor the kernels are not built for, and a field
+// without a velocity net (vW / vb / aW / ab are NULL there: the pack kernels would read through them)
+static int check_vel_call(const nvfi_field_desc* f, const char* call) {
+    if (check_desc(f)) return 2;
+    if (!f->use_vel) return nvfi_fail(2, "%s needs a field with a velocity net (use_vel = 0)", call);
+    return 0;
+}
 extern "C" int nvfi_vel_eval(const nvfi_field_desc* f, int64_t N, const float* xt, float* u6, int gated,
                              void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (check_vel_call(f, "nvfi_vel_eval")) return 2;
     if (N <= 0) return 0;
+    // the published size (nvfi_vel_workspace_bytes) is the contract, as in nvfi_compute_alpha: anything under it is refused here
+    int64_t need = 0; nvfi_vel_workspace_bytes(f, N, &need);
+    if (need > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)need);
     Bump B{(char*)workspace, 0, 0};
     float* fv = B.take<float>(VEL_FRAG_FLOATS);
     float* fa = B.take<float>(VEL_FRAG_FLOATS);
-    if (B.off > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)B.off);
     VelImages VI;
     if (int rc = vel_images(f, gated ? VI_VEL : VI_VEL | VI_ANET, VelImageRoom{fv, fa}, &VI, nullptr, 0, st)) return rc;
     VelEvalArgs a; memset(&a, 0, sizeof(a));
@@ -89,10 +99,13 @@ static void plan_pos(int64_t N, bool own_x6, void* ws, PosPlan* P) {
 extern "C" int nvfi_integrate_pos(const nvfi_field_desc* f, int64_t N, const float* x, const float* t, const float* base,
                                   float* xk, void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (check_vel_call(f, "nvfi_integrate_pos")) return 2;
     if (N <= 0) return 0;
+    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "nvfi_integrate_pos: N too large for one call; chunk the points");
+    int64_t need = 0; nvfi_vel_workspace_bytes(f, N, &need);      // the published size covers every PosPlan (static_assert above)
+    if (need > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)need);
     const WarpKind kind = warp_kind(f, false, true);
     PosPlan P; plan_pos(N, kind == WARP_X6 && !f->frags, workspace, &P);
-    if (P.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)P.total);
     VelImages VI;
     if (int rc = vel_images(f, kind == WARP_X6 ? VI_X6 : (kind == WARP_FP32 ? VI_VEL : 0), VelImageRoom{P.fv, nullptr, nullptr, nullptr, nullptr, P.x6img}, &VI, nullptr, 0, st)) return rc;
     hipLaunchKernelGGL(k_pack_xt, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, P.xw);

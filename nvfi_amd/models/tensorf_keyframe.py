@@ -1224,6 +1224,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
 
     @torch.no_grad()
     def _vel_eval(self, xt, gated):
+        if not self.use_vel:
+            raise _lib.NvfiError("vel / vel_net needs a field with a velocity net (use_vel)")
         L = _lib.lib()
         xt = xt.reshape(-1, 4).contiguous().float()
         N = xt.shape[0]
@@ -1240,6 +1242,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
     def integrate_pos(self, pos_init, t, base_times):
         """RK2 back-advection with per-point times (tensorf_keyframe.py:575-611). Unlike the reference this
         does not mutate its arguments."""
+        if not self.use_vel:
+            raise _lib.NvfiError("integrate_pos needs a field with a velocity net (use_vel)")
         L = _lib.lib()
         x = pos_init.reshape(-1, 3).contiguous().float()
         tt = t.reshape(-1).contiguous().float()

@@ -388,3 +388,64 @@ def test_point_workspace_sizes_are_pinned():
         assert tuple(got) == tuple(w + grow for w in want), name
     nb = C.c_int64(-1)
     assert _lib.lib().nvfi_frag_cache_bytes(C.byref(d), C.byref(nb)) == 0 and nb.value == FRAG_CACHE_BYTES
+
+
+def test_point_queries_refuse_before_anything_is_launched():
+    """nvfi_vel_eval / nvfi_integrate_pos on a field without a velocity net (its vW / vb / aW / ab are NULL), on a descriptor check_desc rejects and
+    on N >= 2^31 - 256; the N limit at nvfi_density_at / nvfi_app_at / nvfi_render_mlp: error 2 with a message, returned before the first HIP
+    call - so this runs where there is no GPU, on host-built descriptors and dummy pointers that nothing may dereference."""
+    import ctypes as C
+    from nvfi_amd import _lib
+    L = _lib.lib()
+    L.nvfi_last_error.restype = C.c_char_p
+    dummy = (C.c_float * 64)()
+    p = C.cast(dummy, C.c_void_p)
+    big = (1 << 31) - 256
+
+    def vel_eval(d, n, gated=0):
+        return L.nvfi_vel_eval(C.byref(d), C.c_int64(n), p, p, C.c_int(gated), p, C.c_int64(256), None)
+
+    def integrate(d, n):
+        return L.nvfi_integrate_pos(C.byref(d), C.c_int64(n), p, p, p, p, p, C.c_int64(256), None)
+
+    def density(d, n):
+        return L.nvfi_density_at(C.byref(d), C.c_int64(n), p, p, p, None)
+
+    def app_at(d, n):
+        return L.nvfi_app_at(C.byref(d), C.c_int64(n), p, p, p, p, C.c_int64(256), None)
+
+    def render_mlp(d, n):
+        return L.nvfi_render_mlp(C.byref(d), C.c_int64(n), p, p, p, p, p, C.c_int64(256), None)
+
+    def refused(rc, *words):
+        msg = L.nvfi_last_error().decode()
+        assert rc == 2 and all(w in msg for w in words), (rc, msg)
+
+    # ---- a field without a velocity net: every pointer of the two nets is NULL
+    d = _plan_desc()
+    d.use_vel = 0
+    for gated in (0, 1):
+        refused(vel_eval(d, 16, gated), "nvfi_vel_eval", "use_vel")
+    refused(integrate(d, 16), "nvfi_integrate_pos", "use_vel")
+    refused(integrate(d, 0), "nvfi_integrate_pos", "use_vel")         # the descriptor is checked before the empty call returns 0
+    # ---- a descriptor the kernels are not built for
+    d = _plan_desc()
+    d.Cd = 16
+    refused(vel_eval(d, 16), "Cd=16")
+    refused(integrate(d, 16), "Cd=16")
+    d = _plan_desc()
+    d.n_samples = 0
+    refused(vel_eval(d, 16), "n_samples")
+    refused(integrate(d, 16), "n_samples")
+    # ---- N that does not fit the kernels' int counters: the limit of nvfi_compute_alpha, at its first refused value and above
+    d = _plan_desc()
+    for n in (big, 1 << 31, 1 << 40):
+        refused(integrate(d, n), "nvfi_integrate_pos", "N too large")
+        refused(density(d, n), "nvfi_density_at", "N too large")
+        refused(app_at(d, n), "nvfi_app_at", "N too large")
+        refused(render_mlp(d, n), "nvfi_render_mlp", "N too large")
+    # ---- one under the limit is NOT refused for its size: the 256-byte workspace is (4), still before any launch
+    assert integrate(d, big - 1) == 4 and app_at(d, big - 1) == 4 and render_mlp(d, big - 1) == 4 and vel_eval(d, 1 << 40) == 4
+    assert "workspace too small" in L.nvfi_last_error().decode()
+    # ---- an empty call stays a no-op
+    assert vel_eval(d, 0) == 0 and integrate(d, 0) == 0 and density(d, 0) == 0 and app_at(d, 0) == 0 and render_mlp(d, 0) == 0
