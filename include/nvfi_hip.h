@@ -331,6 +331,26 @@ int nvfi_mse(const float* x, const float* target, int64_t n, float* loss, float*
 #define NVFI_DEPTH_LDS_MAX 16384
 int nvfi_depth_loss(int64_t n, const float* pred, const float* gt, const int64_t* gt_index, int flags, float grad_scale,
                     float* loss, float* g_pred, int64_t* n_counted, void* stream);
+/* ---- distortion loss on the ray weights (an addition to ABI v5; csrc/raydist.hip; Mip-NeRF 360 eq. 15 - the reference has no such term):
+ *      the samples of a ray are equally spaced (z_j = t_min + step (j + u)), so in normalised distance every interval has the width
+ *      delta = step_size / (far - near) and two midpoints differ by (j - i) delta:
+ *        D_r = delta [ sum_i sum_j w_i w_j |i - j| + (1/3) sum_i w_i^2 ],  loss[0] = (1/R) sum_r D_r (UN-scaled),  per_ray[r] = D_r,
+ *        g_weights[r][i] = grad_scale [* grad_scale_dev[0]] * (delta / R) [ 2 (A_i + B_i) + (2/3) w_i ],  WRITTEN, not accumulated,
+ *        A_i = sum_{j<i} (i - j) w_j, B_i = sum_{j>i} (j - i) w_j (double scans of non-negative terms from either end).
+ *      loss, per_ray, g_weights: each may be NULL and is then left out; the others do not change by a bit.  grad_scale_dev: device float[1]
+ *      (an upstream gradient that never visits the host) or NULL.  One launch of one wave per ray (any S >= 1: the reverse sweep re-reads the
+ *      weights; g_weights must not overlap them) + one launch of one workgroup that sums the R per-ray values (fp64, workspace) in a fixed order: two calls
+ *      give the same bits.  No atomics, no memset, no host synchronisation.  R == 0: loss[0] = 0, nothing else is written.
+ *      workspace: read and written only when loss is not NULL and R > 0 (it holds the R doubles the mean sums); otherwise it may be NULL.
+ *      Errors: 2 (R < 0, S < 1, weights NULL), 4 (a needed workspace that is NULL, smaller than nvfi_ray_distortion_workspace_bytes(R) or not
+ *      8-byte aligned), before any launch. */
+int nvfi_ray_distortion_workspace_bytes(int64_t R, int64_t* bytes);
+int nvfi_ray_distortion(int64_t R, int S, const float* weights /* (R,S) */, float delta,
+                        float grad_scale, const float* grad_scale_dev /* device float[1] multiplied in, or NULL */,
+                        float* loss /* device float[1], un-scaled mean; or NULL */,
+                        float* per_ray /* (R) D_r; or NULL */,
+                        float* g_weights /* (R,S), WRITTEN not accumulated: grad_scale [* *grad_scale_dev] * d loss/d w; or NULL */,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 int nvfi_adam_step(const nvfi_adam_tensor* t, int n_tensors, float beta1, float beta2, float eps, int64_t step, int zero_grad, void* stream);
 
 /* same step with the per-iteration scalars in DEVICE memory (hipGraph replay): hyper_dev[0] = 1/sqrt(1-beta2^step),

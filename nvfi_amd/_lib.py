@@ -71,6 +71,7 @@ EXPORTS = [
     "nvfi_char_workspace_bytes", "nvfi_char_loss",
     "nvfi_depth_loss",
     "nvfi_advect_grad_workspace_bytes", "nvfi_advect_grad",
+    "nvfi_ray_distortion_workspace_bytes", "nvfi_ray_distortion",
 ]
 
 _LIB = None
@@ -103,6 +104,8 @@ def lib():
         L.nvfi_depth_loss.argtypes = [C.c_int64, fp, fp, fp, C.c_int, C.c_float, fp, fp, fp, fp]
         L.nvfi_advect_grad_workspace_bytes.argtypes = [fp, C.c_int64, C.c_float, C.c_float, i64p]
         L.nvfi_advect_grad.argtypes = [fp, C.c_int64, fp, C.c_float, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
+        L.nvfi_ray_distortion_workspace_bytes.argtypes = [C.c_int64, i64p]
+        L.nvfi_ray_distortion.argtypes = [C.c_int64, C.c_int, fp, C.c_float, C.c_float, fp, fp, fp, fp, fp, C.c_int64, fp]
         _LIB = L
     return _LIB
 

@@ -55,6 +55,14 @@ class NVFi(nn.Module):
         """integrate_pos(pos, t, t_target) with gradients to `pos` and the velocity net (TensorVMKeyframeTimeKplane.advect)"""
         return self.nvfi.advect(pos, t, t_target, max_workspace_bytes=max_workspace_bytes)
 
+    def distortion_delta(self):
+        """stepSize / (far - near): the interval width the distortion loss takes (TensorVMKeyframeTimeKplane.distortion_delta)"""
+        return self.nvfi.distortion_delta()
+
+    def distortion_loss(self, weights):
+        """distortion loss of the (R, S) ray weights of a training render, with gradient (TensorVMKeyframeTimeKplane.distortion_loss)"""
+        return self.nvfi.distortion_loss(weights)
+
     def update_nvfi_kwargs(self, kwargs):
         """models/nvfi.py:33-35 writes every checkpoint kwarg into the field's __dict__.  Same effect here, except that the two
         entries the C-ABI descriptor caches on the host (aabb, gridSize) go through the buffer / update_stepSize."""

@@ -23,6 +23,12 @@ from .tensorf_model_utils import AlphaGridMask
 # gradient arena): kept beside the module, keyed weakly
 _RUNTIME = weakref.WeakKeyDictionary()
 
+# render_mse_backward_: the slots of the 64-float `loss` piece of its output buffer, one owner each
+_LOSS_MSE = 0                  # nvfi_render_fwd_mse
+_LOSS_DEPTH = 1                # nvfi_depth_loss: the value ...
+_LOSS_DEPTH_COUNT = 2          # ... and its int64 count of the entries that took part (8-byte aligned: two floats)
+_LOSS_DISTORTION = 4           # nvfi_ray_distortion
+
 
 def _rt(field):
     d = _RUNTIME.get(field)
@@ -1502,7 +1508,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
 
     @torch.no_grad()
     def render_mse_backward_(self, t, ray_o, ray_d, target, white_bg=True, loss_scale=1.0, jitter=None, wait_before_backward=None,
-                             target_depth=None, depth_index=None, depth_weight=1.0, skip_holes=False, check_depth_index=False):
+                             target_depth=None, depth_index=None, depth_weight=1.0, skip_holes=False, check_depth_index=False,
+                             distortion_weight=0.0):
         """Fused-driver form of one TRAINING render of train_nvfi.py:150-178 + its share of loss.backward() (train_nvfi.py:242):
         forward, `loss_scale * F.mse_loss(rgb_map, target)` and the backward of both, with the parameter gradients ACCUMULATED into p.grad
         (which must exist: nvfi_amd.dist.GradBucket, or zeros_like) - no autograd graph, no torch launch: nvfi_render_fwd_mse forms the loss and
@@ -1519,12 +1526,21 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         kernel does not range-check the indices: they are the caller's contract, as pixel_ids drawn for an image of target_depth's size are.
         check_depth_index=True (a debugging aid: one torch min / max and a wait for it, before anything is launched) raises IndexError on an
         index outside the image.  skip_holes=True counts ray i only if its target depth is finite and > 0.  Multi-GPU: every rank
-        normalises its OWN shard of the batch (its own medians); there is no global median."""
+        normalises its OWN shard of the batch (its own medians); there is no global median.
+        distortion_weight (default 0.0: nothing changes, the same launches and the same return values): the distortion loss of the ray
+        weights (Mip-NeRF 360; utils.ray_regs.distortion_loss with delta = self.distortion_delta()).  With a positive weight one
+        nvfi_ray_distortion call between the two halves reads the weights of the forward and writes
+        `loss_scale * distortion_weight * d(distortion loss)/d(weights)` into a scratch (R, S), which the backward half takes as its weight
+        gradient - no torch launch.  The UN-scaled, un-weighted value (0-dim device tensor) is appended as the LAST element of the returned
+        tuple: (loss, rgb, distortion) or (loss, rgb, depth_loss, distortion).  Multi-GPU: every rank's mean is over its OWN shard of the batch."""
         L = _lib.lib()
         if not ray_o.is_cuda or not self.aabb.is_cuda:
             raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
         if self.mask_field is not None:
             raise NotImplementedError("render_mse_backward_ does not drive the mask branch")
+        distortion_weight = float(distortion_weight)
+        if not distortion_weight >= 0.0:
+            raise ValueError(f"distortion_weight must not be negative ({distortion_weight})")
         ray_o = ray_o.reshape(-1, 3).contiguous().float()
         ray_d = ray_d.reshape(-1, 3).contiguous().float()
         target = target.reshape(-1, 3).contiguous().float()
@@ -1543,9 +1559,11 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         nbytes = C.c_int64(0)
         _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        a3, a1 = (3 * R + 63) // 64 * 64, (R + 63) // 64 * 64          # rgb | g_rgb | depth | acc | loss [| g_depth]: one allocation, 256-byte aligned pieces
-        out = torch.empty(2 * a3 + 2 * a1 + 64 + (a1 if target_depth is not None else 0), device=dev)
-        rgb, g_rgb, depth, acc, loss = out[:3 * R].view(R, 3), out[a3:a3 + 3 * R], out[2 * a3:2 * a3 + R], out[2 * a3 + a1:2 * a3 + a1 + R], out[2 * a3 + 2 * a1:]
+        a3, a1 = (3 * R + 63) // 64 * 64, (R + 63) // 64 * 64          # rgb | g_rgb | depth | acc | loss [| g_depth] [| distortion workspace]: one allocation, 256-byte aligned pieces
+        o_gd = 2 * a3 + 2 * a1 + 64
+        o_dw = o_gd + (a1 if target_depth is not None else 0)          # R doubles for nvfi_ray_distortion's mean: 2 * a1 floats
+        out = torch.empty(o_dw + (2 * a1 if distortion_weight > 0.0 else 0), device=dev)
+        rgb, g_rgb, depth, acc, loss = out[:3 * R].view(R, 3), out[a3:a3 + 3 * R], out[2 * a3:2 * a3 + R], out[2 * a3 + a1:2 * a3 + a1 + R], out[o_gd - 64:o_gd]
         g_depth = None
         if target_depth is not None:
             if not target_depth.is_cuda or (depth_index is not None and not depth_index.is_cuda):
@@ -1561,7 +1579,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                         raise IndexError(f"depth_index holds {lo if lo < 0 else hi}, outside the {target_depth.numel()} entries of target_depth")
             elif target_depth.numel() != R:
                 raise ValueError(f"target_depth must hold one depth per ray ({R}) unless depth_index selects from an image")
-            g_depth = out[2 * a3 + 2 * a1 + 64:2 * a3 + 2 * a1 + 64 + R]
+            g_depth = out[o_gd:o_gd + R]
         weights = torch.empty(R, S, device=dev)
         counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
         st = _stream_ptr()
@@ -1569,18 +1587,38 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                                          C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
                                          _lib.ptr(counters), _lib.ptr(target), C.c_float(float(loss_scale)), _lib.ptr(loss), _lib.ptr(g_rgb), st))
         self.last_counters = counters
-        if g_depth is not None:       # loss[1]: the depth loss; the int64 count of the entries that took part sits behind it (loss[2:4])
+        if g_depth is not None:       # the int64 count of the entries that took part sits behind the depth loss
             _lib.check(L.nvfi_depth_loss(C.c_int64(R), _lib.ptr(depth), _lib.ptr(target_depth), _lib.ptr(depth_index),
                                          C.c_int(_lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0), C.c_float(float(loss_scale) * float(depth_weight)),
-                                         _lib.ptr(loss[1:]), _lib.ptr(g_depth), _lib.ptr(loss[2:]), st))
+                                         _lib.ptr(loss[_LOSS_DEPTH:]), _lib.ptr(g_depth), _lib.ptr(loss[_LOSS_DEPTH_COUNT:]), st))
+        g_w = None
+        if distortion_weight > 0.0:
+            dbytes = C.c_int64(0)
+            _lib.check(L.nvfi_ray_distortion_workspace_bytes(C.c_int64(R), C.byref(dbytes)))
+            dws = out[o_dw:]
+            if dbytes.value > dws.numel() * 4:
+                raise _lib.NvfiError(f"nvfi_ray_distortion wants a workspace of {dbytes.value} bytes, {dws.numel() * 4} were set aside")
+            g_w = torch.empty(R, S, device=dev)
+            _lib.check(L.nvfi_ray_distortion(C.c_int64(R), C.c_int(S), _lib.ptr(weights), C.c_float(self.distortion_delta()),
+                                             C.c_float(float(loss_scale) * distortion_weight), None, _lib.ptr(loss[_LOSS_DISTORTION:]), None, _lib.ptr(g_w),
+                                             _lib.ptr(dws), C.c_int64(dws.numel() * 4), st))
         if wait_before_backward is not None:
             torch.cuda.current_stream().wait_stream(wait_before_backward)
         G = self._grads_struct_cached(ps)
         _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_int(int(t_dev is not None)),
-                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, None, C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
-        if g_depth is not None:
-            return loss[0], rgb, loss[1]
-        return loss[0], rgb
+                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, _lib.ptr(g_w), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
+        res = (loss[_LOSS_MSE], rgb) if g_depth is None else (loss[_LOSS_MSE], rgb, loss[_LOSS_DEPTH])
+        return res if g_w is None else res + (loss[_LOSS_DISTORTION],)
+
+    def distortion_delta(self):
+        """width of one sample interval in normalised ray distance s = (z - near) / (far - near): stepSize / (far - near), the `delta` of
+        the distortion loss (every built sampling path spaces a ray's samples by stepSize)"""
+        return float(self._step_host) / (float(self.near_far[1]) - float(self.near_far[0]))
+
+    def distortion_loss(self, weights):
+        """utils.ray_regs.distortion_loss(weights, self.distortion_delta()): the (R, S) weights of a training render -> 0-dim loss with gradient"""
+        from ..utils.ray_regs import distortion_loss
+        return distortion_loss(weights, self.distortion_delta())
 
     def _jitter(self, R, device):
         """Per-ray jitter drawn on the CPU generator like the reference (tensorf_base.py:302-306), staged through a small

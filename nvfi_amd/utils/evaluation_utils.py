@@ -118,7 +118,8 @@ def compute_depth_loss(pred, gt, skip_holes=False):
 
 
 def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, near, far, white_background=True,
-                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False, with_flow=None, gt_depths=None):
+                           savedir=None, update_alpha_mask=True, device=None, with_ssim=False, with_flow=None, gt_depths=None,
+                           with_distortion=False):
     """Eval driver (train_nvfi.py:395-459 without the dataset / wandb plumbing): optional `updateAlphaMask` at the current grid
     (`:413`), one `Renderer.render(mode='test')` per (pose, time) frame (`:437`), 8-bit PNGs named r_%03d.png (`:449-451`,
     written with PIL - imageio is not a dependency here) and per-frame / mean PSNR against `targets` (H,W,3 in [0,1]).
@@ -129,7 +130,10 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     (N,H,W,2), the optical flow over dt in pixels; with `savedir` its colour coding (utils.flow_vis.flow_to_rgb) is written as r_%03d_flow.png.
     gt_depths (default off: N depth frames (H,W), 0 / inf / NaN where the sensor saw nothing) adds "depth_loss": [..] and "mean_depth_loss": the
     median-normalised depth loss of every rendered depth map against its frame (compute_depth_loss with skip_holes=True: one launch per frame
-    on the 640 000 entries of an 800 x 800 frame; the values come to the host once, after the loop)."""
+    on the 640 000 entries of an 800 x 800 frame; the values come to the host once, after the loop).
+    with_distortion=True adds "distortion": [..] and "mean_distortion", the distortion loss of every frame's ray weights
+    (utils.ray_regs.distortion_loss_raw with the field's distortion_delta(): one call per frame), and "distortion_maps" (N,H,W), its per-pixel
+    value D_r: a floater map - a frame whose mean jumps has a floater, the map shows where."""
     import numpy as np
     from ..models import Camera
     from .metrics import mse2psnr, ssim_frames
@@ -137,7 +141,10 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     nvfi.eval()
     if update_alpha_mask:
         nvfi.nvfi.updateAlphaMask(nvfi.nvfi.gridSize)
-    imgs, psnrs, ssims, flows, dlosses = [], [], [], [], []
+    imgs, psnrs, ssims, flows, dlosses, dists, dmaps = [], [], [], [], [], [], []
+    if with_distortion:
+        from .ray_regs import distortion_loss_raw
+        delta = nvfi.distortion_delta()
     with torch.no_grad():
         for idx in range(len(poses)):
             pose = torch.as_tensor(poses[idx], dtype=torch.float32, device=device)
@@ -151,6 +158,11 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
                 flows.append(res[6].reshape(H, W, 2))
             if gt_depths is not None:
                 dlosses.append(compute_depth_loss(res[1], torch.as_tensor(gt_depths[idx], dtype=torch.float32, device=device), skip_holes=True))
+            if with_distortion:
+                wts = res[3].reshape(H * W, -1)
+                d_loss, _, d_map = distortion_loss_raw(wts, delta, out=(torch.empty((), device=wts.device), None, torch.empty(H * W, device=wts.device)))
+                dists.append(d_loss)
+                dmaps.append(d_map.reshape(H, W))
             rgb = rgb.reshape(H, W, 3)
             if targets is not None:
                 tgt = torch.as_tensor(targets[idx], dtype=torch.float32, device=device).reshape(H, W, 3)
@@ -179,6 +191,10 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     if gt_depths is not None:
         out["depth_loss"] = torch.stack(dlosses).cpu().tolist() if dlosses else []
         out["mean_depth_loss"] = (sum(out["depth_loss"]) / len(out["depth_loss"])) if dlosses else None
+    if with_distortion:
+        out["distortion"] = torch.stack(dists).cpu().tolist() if dists else []
+        out["mean_distortion"] = (sum(out["distortion"]) / len(out["distortion"])) if dists else None
+        out["distortion_maps"] = torch.stack(dmaps).cpu().numpy() if dmaps else np.zeros((0, H, W), np.float32)
     return out
 
 
