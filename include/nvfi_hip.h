@@ -351,6 +351,50 @@ int nvfi_ray_distortion(int64_t R, int S, const float* weights /* (R,S) */, floa
                         float* per_ray /* (R) D_r; or NULL */,
                         float* g_weights /* (R,S), WRITTEN not accumulated: grad_scale [* *grad_scale_dev] * d loss/d w; or NULL */,
                         void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- optical-flow supervision of a TRAINING render (an addition to ABI v5; csrc/flowloss.hip; not in the reference - the definition's source is
+ *      nvfi_render_flow above): the flow map of a render nvfi_render_fwd* made with NVFI_TRAIN, of R rays at HOST-scalar time t, its loss against
+ *      a target flow, and all gradients.
+ *        M_r   the appearance-masked samples of ray r: the workspace's mlist / off_m AS THE RENDER MADE THEM (w > weight_thres is not re-evaluated)
+ *        w_j   the render's fp32 weights;  z_j the sample depth the render used (xw.w: jitter and the t_min rule are in it)
+ *        x_j   = normalize_coord(o_r + d_r z_j), the UN-warped position at time t, fp32;  s = aabbSize / 2
+ *        Phi   = integrate_pos(x, t, t + dt) with every rule of nvfi_advect_grad on the uniform schedule; more than 64 steps: error 2; dt == 0: identity
+ *        pi    the projection of nvfi_render_flow for the camera (pose3x4 - a DEVICE pointer -, H, W, focal); P = aabb_min + (x + 1) s
+ *        a sample whose displaced point has -c_z < 1e-3 contributes nothing, and its gradient is exactly zero.  Only the DISPLACED point is
+ *        guarded: a sample whose ORIGINAL point has -c_z == 0 gives a non-finite value (the caller keeps the samples in front of the camera)
+ *        flow2d[r] (R,2) = sum_{j in M_r} w_j (pi(P'_j) - pi(P_j))   pixels, an ordered sum: repeats bit for bit
+ *        ray r is VALID when (valid == NULL or valid[r] != 0) and both target components are finite; n = the number of valid rays
+ *        e_r = flow2d[r] - target[r];  loss = (1 / (2 n)) sum_valid sum_c rho(e_rc);  kind 0: rho(e) = e^2;  kind 1: torch's huber_loss(huber_delta)
+ *        element form;  n == 0: loss = 0 and all gradients exactly zero.  The mean is formed in a fixed order with fp64 partials.  n stays on the
+ *        device: loss is device float[2] = (loss, n).
+ *      Gradients are grad_scale [* grad_scale_dev[0]] times the following, every discrete decision held fixed:
+ *        g_weights[r][j] = g_r . (pi(P'_j) - pi(P_j)) for j in M_r, 0 elsewhere; the (R,S) array is WRITTEN, with NVFI_FLOWLOSS_ADD_GW in loss_flags
+ *                          ADDED to (composes with the scratch of nvfi_ray_distortion);  g_r = rho'(e_r) / (2 n), 0 for an invalid ray
+ *        g_xd[j] = w_j s (.) R_cam Jpi(c'_j)^T g_r, with d = -c_z: du/dc = focal (1/d, 0, c_x/d^2), dv/dc = -focal (0, 1/d, c_y/d^2);  it goes through
+ *                          the adjoint of Phi into weight_net (grads->vW / vb, ACCUMULATED) and reaches nothing else: rays, t, dt, the pose, the
+ *                          planes and a_weight_net get nothing; no second order.
+ *      nvfi_flow_loss_fwd: after the training forward, before its backward.  render_workspace is READ only and left bit-identical; all scratch is
+ *      in `workspace` (nvfi_flow_loss_workspace_bytes with the SAME R, t, dt, chunk_cap), which must stay untouched until the last
+ *      nvfi_flow_loss_bwd of the call.  loss, flow2d, g_weights: each may be NULL.
+ *      nvfi_flow_loss_bwd: the entries [first, first + chunk_cap) of the masked list, clipped on the DEVICE to the masked count, through the chain of
+ *      nvfi_advect_grad; call it for first = 0, chunk_cap, 2 chunk_cap, ... < R * n_samples.  A chunk wholly beyond the masked count launches
+ *      kernels that exit at once and changes no gradient.  dt == 0: nothing is launched.
+ *      No host synchronisation, the masked count never reaches the host, no float atomics outside the weight-gradient reduce.
+ *      Errors, before any launch: (2) flags without NVFI_TRAIN, use_vel == 0, vel_fp16 modes 1 / 2, more than 64 RK2 steps, pose3x4 or target NULL,
+ *      R <= 0, an unknown kind / loss_flags; (4) a workspace that is NULL, too small or not 16-byte aligned. */
+#define NVFI_FLOWLOSS_ADD_GW 1
+int nvfi_flow_loss_workspace_bytes(const nvfi_field_desc* f, int64_t R, float t, float dt, int64_t chunk_cap, int64_t* bytes);
+int nvfi_flow_loss_fwd(const nvfi_field_desc* f, int64_t R, const float* rays_o, const float* rays_d, float t, float dt, int flags,
+                       const float* weights /* (R,S) of the render */,
+                       const float* pose3x4, int H, int W, float focal,
+                       const float* target /* (R,2) */, const uint8_t* valid /* (R) or NULL */, int kind, float huber_delta,
+                       float grad_scale, const float* grad_scale_dev /* device float[1] multiplied in, or NULL */, int loss_flags,
+                       float* loss /* device float[2]: un-scaled loss, n; or NULL */, float* flow2d /* (R,2) or NULL */,
+                       float* g_weights /* (R,S) or NULL */,
+                       const void* render_workspace, int64_t render_workspace_bytes, int64_t chunk_cap,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int nvfi_flow_loss_bwd(const nvfi_field_desc* f, int64_t R, float t, float dt, int64_t first, int64_t chunk_cap,
+                       const nvfi_grads* grads /* vW / vb ACCUMULATED, the rest ignored */,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 int nvfi_adam_step(const nvfi_adam_tensor* t, int n_tensors, float beta1, float beta2, float eps, int64_t step, int zero_grad, void* stream);
 
 /* same step with the per-iteration scalars in DEVICE memory (hipGraph replay): hyper_dev[0] = 1/sqrt(1-beta2^step),

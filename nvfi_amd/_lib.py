@@ -10,6 +10,7 @@ fp = C.c_void_p
 NVFI_TRAIN, NVFI_WHITE_BG, NVFI_TRANSFER, NVFI_WANT_MASK, NVFI_BWD_FORK, NVFI_WANT_FLOW, NVFI_WANT_SELECT = 1, 2, 4, 8, 16, 32, 64
 NCOUNTERS = 8
 NVFI_DEPTH_SKIP_HOLES = 1
+NVFI_FLOWLOSS_ADD_GW = 1
 NVFI_DEPTH_LDS_MAX = 16384      # nvfi_depth_loss keeps both maps in LDS up to this many entries (include/nvfi_hip.h)
 
 
@@ -72,6 +73,7 @@ EXPORTS = [
     "nvfi_depth_loss",
     "nvfi_advect_grad_workspace_bytes", "nvfi_advect_grad",
     "nvfi_ray_distortion_workspace_bytes", "nvfi_ray_distortion",
+    "nvfi_flow_loss_workspace_bytes", "nvfi_flow_loss_fwd", "nvfi_flow_loss_bwd",
 ]
 
 _LIB = None
@@ -106,6 +108,10 @@ def lib():
         L.nvfi_advect_grad.argtypes = [fp, C.c_int64, fp, C.c_float, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
         L.nvfi_ray_distortion_workspace_bytes.argtypes = [C.c_int64, i64p]
         L.nvfi_ray_distortion.argtypes = [C.c_int64, C.c_int, fp, C.c_float, C.c_float, fp, fp, fp, fp, fp, C.c_int64, fp]
+        L.nvfi_flow_loss_workspace_bytes.argtypes = [fp, C.c_int64, C.c_float, C.c_float, C.c_int64, i64p]
+        L.nvfi_flow_loss_fwd.argtypes = [fp, C.c_int64, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp, fp, C.c_int, C.c_float,
+                                         C.c_float, fp, C.c_int, fp, fp, fp, fp, C.c_int64, C.c_int64, fp, C.c_int64, fp]
+        L.nvfi_flow_loss_bwd.argtypes = [fp, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, fp, fp, C.c_int64, fp]
         _LIB = L
     return _LIB
 

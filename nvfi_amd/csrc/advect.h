@@ -1,0 +1,22 @@
+// advect.h - the host-side entry to the adjoint chain of integrate_pos that advect.hip (nvfi_advect_grad) and flowloss.hip (nvfi_flow_loss_bwd)
+// share: the plan of one chunk of points and the launches behind the caller's own pack kernel.  Host code only: no kernel is declared here.
+#pragma once
+#include "common.h"
+#include "frags.h"
+
+struct AdvectPlan {
+    int* count; int* list; float4* xw; float4* gxk;
+    float *vel_frag, *vel_x4, *vel_x4b; void* x6img;
+    float *slabs, *zst, *x0st, *gst, *rec;
+    int64_t cap_tiles, total;
+};
+// the training render's forward kernel family; its opt-in fp16-input forward (vel_fp16 bit 2) is the render's alone: integrate_pos never takes it
+WarpKind advect_kind(const nvfi_field_desc* f);
+// the rooms of a chunk of N points and nsteps RK2 steps in `ws` (NULL: sizes only, P->total)
+void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKind kind, void* ws, AdvectPlan* P);
+// Behind a pack kernel of the caller's on `st` that has written P.xw (the dense starting positions), P.gxk (the upstream gradient at the
+// advected positions), P.list (the identity) and P.count[0] (the DEVICE count of points, <= N): the weight images, the stash-writing uniform
+// warp, the unfused adjoint (which stores the gradient at the start into g_x when that is not NULL) and the six weight-gradient jobs,
+// ACCUMULATED into grads->vW / vb.  N is the launch capacity; nsteps >= 1.
+int advect_chain(const nvfi_field_desc* f, const AdvectPlan& P, int64_t N, int nsteps, const float* dts, const float* tcs, WarpKind kind,
+                 float* g_x, const nvfi_grads* grads, hipStream_t st);

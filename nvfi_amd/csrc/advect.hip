@@ -9,6 +9,7 @@
 //   launch_rk2_split_bwd(gx0)                      k_rk2_split_bwd<true>: the unfused adjoint, which also stores the gradient at the start
 //   launch_vel_wgrad(fused_nslab = 0)              six ring jobs + the slab reduce, ACCUMULATED into grads->vW / vb
 // The adjoint is always the unfused pair, whatever NVFI_RK2_FUSE says: the fused kernel (vel_fuse.hip) has no position output.
+// Everything behind the pack kernel is advect_chain (advect.h), the host-side entry nvfi_flow_loss_bwd (flowloss.hip) shares.
 // All on the caller's stream, no host synchronisation.
 #include <string.h>
 #include "common.h"
@@ -17,6 +18,7 @@
 #include "render.h"
 #include "frags.h"
 #include "x6.h"
+#include "advect.h"
 
 #define ADV_NSLAB 256                            // slab capacity of a weight-gradient job (one per CU), as the render's
 #define ADV_SLAB_FLOATS (128 * 128 + 128)        // (launch_vel_wgrad strides the six jobs by nslab slabs of this size)
@@ -37,14 +39,8 @@ __global__ __launch_bounds__(256) void k_advect_copy(int64_t n, const float* __r
     if (i < n) dst[i] = src[i];
 }
 
-struct AdvectPlan {
-    int* count; int* list; float4* xw; float4* gxk;
-    float *vel_frag, *vel_x4, *vel_x4b; void* x6img;
-    float *slabs, *zst, *x0st, *gst, *rec;
-    int64_t cap_tiles, total;
-};
 // sized like plan_render's `nsteps > 0 && train` block: whole 128-point workgroups of stash tiles, two evaluations per step, the records
-static void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKind kind, void* ws, AdvectPlan* P) {
+void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKind kind, void* ws, AdvectPlan* P) {
     Bump B{(char*)ws, 0, 0};
     const bool own = !f->frags;                  // without a fragment cache the images are packed into the call's own room
     P->cap_tiles = (N + WG_SAMPLES - 1) / WG_SAMPLES * 4;
@@ -66,7 +62,7 @@ static void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKin
 }
 
 // the training render's forward kernel family; its opt-in fp16-input forward (vel_fp16 bit 2) is the render's alone: integrate_pos never takes it
-static WarpKind advect_kind(const nvfi_field_desc* f) {
+WarpKind advect_kind(const nvfi_field_desc* f) {
     const WarpKind k = warp_kind(f, true, false);
     return k == WARP_FP16IN ? (sw(NVFI_RK2_X6) ? WARP_X6 : WARP_FP32) : k;
 }
@@ -105,11 +101,17 @@ extern "C" int nvfi_advect_grad(const nvfi_field_desc* f, int64_t N, const float
     const WarpKind kind = advect_kind(f);
     AdvectPlan P; plan_advect(f, N, nsteps, kind, workspace, &P);
     if (!workspace || P.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld bytes, got %lld", (long long)P.total, (long long)workspace_bytes);
+    hipLaunchKernelGGL(k_advect_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, g_xk, P.xw, P.gxk, P.list, P.count);
+    LAUNCHCK();
+    return advect_chain(f, P, N, nsteps, dts, tcs, kind, g_x, grads, st);
+}
+
+// the launches behind the caller's pack kernel (advect.h): shared with nvfi_flow_loss_bwd (flowloss.hip)
+int advect_chain(const nvfi_field_desc* f, const AdvectPlan& P, int64_t N, int nsteps, const float* dts, const float* tcs, WarpKind kind,
+                 float* g_x, const nvfi_grads* grads, hipStream_t st) {
     VelImages VI;
     const unsigned need = VI_VEL | VI_X4B | (kind == WARP_X6 ? VI_X6 : VI_X4F);
     if (int rc = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, nullptr}, &VI, nullptr, 0, st)) return rc;
-    hipLaunchKernelGGL(k_advect_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, g_xk, P.xw, P.gxk, P.list, P.count);
-    LAUNCHCK();
     Rk2Args ra; memset(&ra, 0, sizeof(ra));
     ra.f = *f; ra.Wv = VI.VW; ra.count = P.count; ra.list = P.list; ra.xw = P.xw; ra.xout = nullptr;
     ra.nsteps = nsteps; ra.sched = nullptr;

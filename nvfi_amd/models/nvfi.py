@@ -63,6 +63,10 @@ class NVFi(nn.Module):
         """distortion loss of the (R, S) ray weights of a training render, with gradient (TensorVMKeyframeTimeKplane.distortion_loss)"""
         return self.nvfi.distortion_loss(weights)
 
+    def flow_loss(self, weights, dt, camera, target_flow, **kw):
+        """optical-flow supervision of a training render, with gradient (TensorVMKeyframeTimeKplane.flow_loss)"""
+        return self.nvfi.flow_loss(weights, dt, camera, target_flow, **kw)
+
     def update_nvfi_kwargs(self, kwargs):
         """models/nvfi.py:33-35 writes every checkpoint kwarg into the field's __dict__.  Same effect here, except that the two
         entries the C-ABI descriptor caches on the host (aabb, gridSize) go through the buffer / update_stepSize."""

@@ -28,6 +28,7 @@ _LOSS_MSE = 0                  # nvfi_render_fwd_mse
 _LOSS_DEPTH = 1                # nvfi_depth_loss: the value ...
 _LOSS_DEPTH_COUNT = 2          # ... and its int64 count of the entries that took part (8-byte aligned: two floats)
 _LOSS_DISTORTION = 4           # nvfi_ray_distortion
+_LOSS_FLOW = 6                 # nvfi_flow_loss_fwd: the value and, in the next slot, n (the number of rays that counted)
 
 
 def _rt(field):
@@ -468,6 +469,50 @@ class _AdvectFn(torch.autograd.Function):
             _lib.check(L.nvfi_advect_grad(C.byref(desc), C.c_int64(n), _lib.ptr(x[i:i + n]), t, t1, _lib.ptr(g[i:i + n]),
                                           None if gx is None else _lib.ptr(gx[i:i + n]), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
         return (None, gx, None, None, None) + tuple(grads)
+
+
+class _FlowLossFn(torch.autograd.Function):
+    """autograd boundary around nvfi_flow_loss_fwd / nvfi_flow_loss_bwd (include/nvfi_hip.h), built like _AdvectFn: the forward runs behind the
+    training render whose backward node `node` still holds its workspace and forms the value, d loss / d weights and the per-entry gradient at
+    the displaced points in the call's own workspace; the backward runs the adjoint of integrate_pos chunk by chunk on that workspace and hands
+    d loss / d weights to autograd, which carries it into _RenderFn.backward as g_weights."""
+
+    @staticmethod
+    def forward(ctx, field, weights, node, dt, camera, target, valid, kind, huber_delta, max_ws, *params):
+        from ..utils import flow_loss as fl
+        rays_o, rays_d, w_saved = node.saved_tensors[:3]
+        desc = field._desc(field._render_params()[:19] + list(params))
+        desc.vel_fp16 = node.vel_fp16
+        want_gw = ctx.needs_input_grad[1]
+        call = fl.flow_loss_raw(desc, node.ws, node.flags, rays_o, rays_d, w_saved, node.t, dt, camera, target, valid=valid, kind=kind,
+                                huber_delta=huber_delta, g_weights=None if want_gw else False, max_workspace_bytes=max_ws)
+        field.last_flow_chunks, field.last_flow_workspace_bytes = call["chunks"], call["workspace"].numel()
+        field.last_flow2d, field.last_flow_n = call["flow2d"], call["loss"][1]
+        ctx.field, ctx.call, ctx.vel_fp16 = field, call, node.vel_fp16
+        ctx.save_for_backward(*params)
+        return call["loss"][0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ..utils import flow_loss as fl
+        params = list(ctx.saved_tensors)
+        field, call = ctx.field, ctx.call
+        if call is None:
+            raise ValueError("flow_loss: the workspace of this call was released by its first backward; a second backward needs a new flow_loss call")
+        desc = field._desc(field._render_params()[:19] + params)
+        desc.vel_fp16 = ctx.vel_fp16
+        need = ctx.needs_input_grad[10:]
+        grads = _zero_grads(params, need)          # the plain path of _AdvectFn.backward: fresh zero gradients, no arena, no side streams
+        if any(need):
+            fl.flow_loss_backward_raw(desc, call, field._grads_struct_vel(list(grads) + [None] * 12))
+        g = g.detach().float()
+        for gr in grads:                           # the upstream gradient never visits the host
+            if gr is not None:
+                gr.mul_(g)
+        g_w = call["g_weights"] * g if ctx.needs_input_grad[1] else None
+        ctx.call = None
+        return (None, g_w) + (None,) * 8 + tuple(grads)
 
 
 class TensorVMKeyframeTimeKplane(nn.Module):
@@ -1509,7 +1554,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
     @torch.no_grad()
     def render_mse_backward_(self, t, ray_o, ray_d, target, white_bg=True, loss_scale=1.0, jitter=None, wait_before_backward=None,
                              target_depth=None, depth_index=None, depth_weight=1.0, skip_holes=False, check_depth_index=False,
-                             distortion_weight=0.0):
+                             distortion_weight=0.0, target_flow=None, flow_dt=None, flow_camera=None, flow_weight=1.0, flow_valid=None,
+                             flow_kind="l2", flow_huber_delta=1.0, flow_max_workspace_bytes=1 << 30):
         """Fused-driver form of one TRAINING render of train_nvfi.py:150-178 + its share of loss.backward() (train_nvfi.py:242):
         forward, `loss_scale * F.mse_loss(rgb_map, target)` and the backward of both, with the parameter gradients ACCUMULATED into p.grad
         (which must exist: nvfi_amd.dist.GradBucket, or zeros_like) - no autograd graph, no torch launch: nvfi_render_fwd_mse forms the loss and
@@ -1532,7 +1578,16 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         nvfi_ray_distortion call between the two halves reads the weights of the forward and writes
         `loss_scale * distortion_weight * d(distortion loss)/d(weights)` into a scratch (R, S), which the backward half takes as its weight
         gradient - no torch launch.  The UN-scaled, un-weighted value (0-dim device tensor) is appended as the LAST element of the returned
-        tuple: (loss, rgb, distortion) or (loss, rgb, depth_loss, distortion).  Multi-GPU: every rank's mean is over its OWN shard of the batch."""
+        tuple: (loss, rgb, distortion) or (loss, rgb, depth_loss, distortion).  Multi-GPU: every rank's mean is over its OWN shard of the batch.
+        target_flow (default None: nothing changes, the same launches and the same return values): optical-flow supervision (flow_loss; the
+        definition is in include/nvfi_hip.h).  (R, 2) target flow in pixels over flow_dt for the camera flow_camera, flow_valid an optional
+        per-ray mask, flow_kind "l2" / "huber".  One nvfi_flow_loss_fwd between the two halves, behind the distortion call (it then ADDS its
+        `loss_scale * flow_weight * d(flow loss)/d(weights)` to that call's scratch), and the chunked nvfi_flow_loss_bwd beside the backward
+        half, into the same gradient buffers - no torch launch, PROVIDED the inputs arrive ready: target_flow a contiguous float32 (R, 2) device
+        tensor, the pose of flow_camera a float32 device tensor and flow_valid a contiguous uint8 device tensor.  A host pose is copied to the
+        device and a bool / float mask converted with a torch launch on every call (utils.flow_loss.flow_loss_raw); convert them once outside
+        a loop or a captured graph.  The UN-scaled, un-weighted value (0-dim device tensor) is appended behind the distortion value.  The mask
+        branch and DeviceTime renders raise NotImplementedError."""
         L = _lib.lib()
         if not ray_o.is_cuda or not self.aabb.is_cuda:
             raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
@@ -1541,6 +1596,13 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         distortion_weight = float(distortion_weight)
         if not distortion_weight >= 0.0:
             raise ValueError(f"distortion_weight must not be negative ({distortion_weight})")
+        if target_flow is not None:
+            if getattr(t, "dev", None) is not None:
+                raise NotImplementedError("render_mse_backward_: the flow term does not support DeviceTime renders")
+            if flow_dt is None or flow_camera is None:
+                raise ValueError("target_flow needs flow_dt and flow_camera")
+            if not self.use_vel:
+                raise _lib.NvfiError("the flow term needs a field with a velocity net (use_vel)")
         ray_o = ray_o.reshape(-1, 3).contiguous().float()
         ray_d = ray_d.reshape(-1, 3).contiguous().float()
         target = target.reshape(-1, 3).contiguous().float()
@@ -1602,13 +1664,60 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             _lib.check(L.nvfi_ray_distortion(C.c_int64(R), C.c_int(S), _lib.ptr(weights), C.c_float(self.distortion_delta()),
                                              C.c_float(float(loss_scale) * distortion_weight), None, _lib.ptr(loss[_LOSS_DISTORTION:]), None, _lib.ptr(g_w),
                                              _lib.ptr(dws), C.c_int64(dws.numel() * 4), st))
+        flow_call = None
+        if target_flow is not None:
+            from ..utils import flow_loss as fl
+            add = g_w is not None
+            flow_call = fl.flow_loss_raw(desc, ws, flags, ray_o, ray_d, weights, t, flow_dt, flow_camera, target_flow, valid=flow_valid, kind=flow_kind,
+                                         huber_delta=flow_huber_delta, grad_scale=float(loss_scale) * float(flow_weight), g_weights=g_w, add_gw=add,
+                                         loss=loss[_LOSS_FLOW:_LOSS_FLOW + 2], flow2d=False, max_workspace_bytes=flow_max_workspace_bytes)
+            g_w_flow = flow_call["g_weights"]
+            self.last_flow_chunks, self.last_flow_workspace_bytes = flow_call["chunks"], flow_call["workspace"].numel()
         if wait_before_backward is not None:
             torch.cuda.current_stream().wait_stream(wait_before_backward)
         G = self._grads_struct_cached(ps)
         _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_int(int(t_dev is not None)),
-                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, _lib.ptr(g_w), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
+                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, _lib.ptr(g_w if flow_call is None else g_w_flow), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
         res = (loss[_LOSS_MSE], rgb) if g_depth is None else (loss[_LOSS_MSE], rgb, loss[_LOSS_DEPTH])
-        return res if g_w is None else res + (loss[_LOSS_DISTORTION],)
+        if g_w is not None:
+            res = res + (loss[_LOSS_DISTORTION],)
+        if flow_call is not None:
+            fl.flow_loss_backward_raw(desc, flow_call, G)
+            res = res + (loss[_LOSS_FLOW],)
+        return res
+
+    def flow_loss(self, weights, dt, camera, target_flow, valid=None, kind="l2", huber_delta=1.0, weight_grad=True, max_workspace_bytes=1 << 30):
+        """Optical-flow supervision of a training render (include/nvfi_hip.h: nvfi_flow_loss_fwd / _bwd; utils/flow_loss.py) -> 0-dim loss
+        with gradient.  `weights` must be the (R, S) tensor that a training `forward` of this field returned - the tensor itself, with its
+        autograd node, whose workspace (masked list, sample depths) the call reads; anything else, or a render whose backward has already run,
+        raises ValueError.  It need not be the most recent render: every render owns its workspace until its backward.  A render made with a
+        mask_field attached (the mask branch) raises NotImplementedError, as in render_mse_backward_.
+        flow2d[r] = sum_j w_j (pi(integrate_pos(x_j, t, t + dt)) - pi(x_j)) over the render's appearance-masked samples, pi the projection of
+        `camera` ((pose3x4, H, W, focal) or an object with pose / height / width / focal); loss = (1 / (2 n)) sum over the n valid rays (valid[r]
+        != 0 and a finite target) and both components of (flow2d - target_flow)^2 (kind="l2") or of torch's huber element (kind="huber").
+        The gradient reaches the weights (and through the render backward everything the render depends on; weight_grad=False leaves the
+        weights without gradient) and the 12 tensors of vel_net.weight_net through the adjoint of integrate_pos, every gate / rejection / guard
+        decision held fixed; nothing else, no second order.  The backward splits the R * nSamples capacity of the masked list into chunks
+        whose plan stays under max_workspace_bytes (self.last_flow_chunks, self.last_flow_workspace_bytes); the workspace lives from this call
+        to its backward.  self.last_flow2d holds the (R, 2) flow map, self.last_flow_n the device-side count of valid rays."""
+        if not self.use_vel:
+            raise _lib.NvfiError("flow_loss needs a field with a velocity net (use_vel)")
+        if not (isinstance(weights, torch.Tensor) and weights.is_cuda):
+            raise _lib.NvfiError("flow_loss needs the weights of a render on the GPU (no CPU fallback exists)")
+        node = weights.grad_fn
+        if not isinstance(node, _RenderFn._backward_cls) or getattr(node, "field", None) is not self or not (getattr(node, "flags", 0) & _lib.NVFI_TRAIN):
+            raise ValueError("flow_loss: `weights` must be the tensor a training forward of this field returned (with its autograd node)")
+        if node.flags & _lib.NVFI_WANT_MASK:
+            raise NotImplementedError("flow_loss: renders of the mask branch (a mask_field attached) are not supported")
+        if node.ws is None:
+            raise ValueError("flow_loss: the workspace of that render was released by its backward; call flow_loss before backward")
+        if node.t_on_device:
+            raise NotImplementedError("flow_loss: DeviceTime renders are not supported (the flow loss plans with a host-scalar time)")
+        wparams = self._render_params()[19:31]
+        w_in = weights if weight_grad else weights.detach()
+        if not torch.is_grad_enabled():
+            w_in = weights.detach()
+        return _FlowLossFn.apply(self, w_in, node, float(dt), camera, target_flow, valid, kind, float(huber_delta), int(max_workspace_bytes), *wparams)
 
     def distortion_delta(self):
         """width of one sample interval in normalised ray distance s = (z - near) / (far - near): stepSize / (far - near), the `delta` of

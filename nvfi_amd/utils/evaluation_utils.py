@@ -119,7 +119,7 @@ def compute_depth_loss(pred, gt, skip_holes=False):
 
 def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, near, far, white_background=True,
                            savedir=None, update_alpha_mask=True, device=None, with_ssim=False, with_flow=None, gt_depths=None,
-                           with_distortion=False):
+                           with_distortion=False, gt_flows=None, flow_dt=None, flow_valid=None):
     """Eval driver (train_nvfi.py:395-459 without the dataset / wandb plumbing): optional `updateAlphaMask` at the current grid
     (`:413`), one `Renderer.render(mode='test')` per (pose, time) frame (`:437`), 8-bit PNGs named r_%03d.png (`:449-451`,
     written with PIL - imageio is not a dependency here) and per-frame / mean PSNR against `targets` (H,W,3 in [0,1]).
@@ -133,7 +133,11 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     on the 640 000 entries of an 800 x 800 frame; the values come to the host once, after the loop).
     with_distortion=True adds "distortion": [..] and "mean_distortion", the distortion loss of every frame's ray weights
     (utils.ray_regs.distortion_loss_raw with the field's distortion_delta(): one call per frame), and "distortion_maps" (N,H,W), its per-pixel
-    value D_r: a floater map - a frame whose mean jumps has a floater, the map shows where."""
+    value D_r: a floater map - a frame whose mean jumps has a floater, the map shows where.
+    gt_flows (default off: N target flow frames (H,W,2) in pixels over flow_dt, which must be given and takes the place of with_flow; flow_valid
+    optional N masks (H,W), non-finite targets never count) renders every frame through Renderer.render_flow and adds "epe": [..] and
+    "mean_epe", the end-point error of every frame: the mean of |flow2d - gt|_2 over its valid pixels (NaN for a frame without one); torch ops
+    on the device, the values come to the host once, after the loop."""
     import numpy as np
     from ..models import Camera
     from .metrics import mse2psnr, ssim_frames
@@ -141,7 +145,13 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     nvfi.eval()
     if update_alpha_mask:
         nvfi.nvfi.updateAlphaMask(nvfi.nvfi.gridSize)
-    imgs, psnrs, ssims, flows, dlosses, dists, dmaps = [], [], [], [], [], [], []
+    imgs, psnrs, ssims, flows, dlosses, dists, dmaps, epes = [], [], [], [], [], [], [], []
+    if gt_flows is not None:
+        if flow_dt is None:
+            raise ValueError("gt_flows needs flow_dt, the time span the target flow covers")
+        if with_flow is not None and float(with_flow) != float(flow_dt):
+            raise ValueError(f"with_flow={with_flow} and flow_dt={flow_dt} disagree: one flow map is rendered per frame")
+        with_flow = flow_dt
     if with_distortion:
         from .ray_regs import distortion_loss_raw
         delta = nvfi.distortion_delta()
@@ -156,6 +166,13 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
                 res = renderer.render_flow(float(times[idx]), cam.rays.to(device), float(with_flow), camera=cam, white_background=white_background)
                 rgb = res[0]
                 flows.append(res[6].reshape(H, W, 2))
+                if gt_flows is not None:
+                    gt = torch.as_tensor(gt_flows[idx], dtype=torch.float32, device=device).reshape(H, W, 2)
+                    ok = torch.isfinite(gt).all(-1)
+                    if flow_valid is not None:
+                        ok = ok & (torch.as_tensor(flow_valid[idx], device=device).reshape(H, W) != 0)
+                    err = torch.linalg.vector_norm(flows[-1] - torch.where(ok[..., None], gt, torch.zeros_like(gt)), dim=-1)
+                    epes.append(torch.where(ok, err, torch.zeros_like(err)).sum() / ok.sum())
             if gt_depths is not None:
                 dlosses.append(compute_depth_loss(res[1], torch.as_tensor(gt_depths[idx], dtype=torch.float32, device=device), skip_holes=True))
             if with_distortion:
@@ -191,6 +208,9 @@ def render_test_evaluation(nvfi, renderer, poses, times, targets, H, W, focal, n
     if gt_depths is not None:
         out["depth_loss"] = torch.stack(dlosses).cpu().tolist() if dlosses else []
         out["mean_depth_loss"] = (sum(out["depth_loss"]) / len(out["depth_loss"])) if dlosses else None
+    if gt_flows is not None:
+        out["epe"] = torch.stack(epes).cpu().tolist() if epes else []
+        out["mean_epe"] = (sum(out["epe"]) / len(out["epe"])) if epes else None
     if with_distortion:
         out["distortion"] = torch.stack(dists).cpu().tolist() if dists else []
         out["mean_distortion"] = (sum(out["distortion"]) / len(out["distortion"])) if dists else None
