@@ -1,6 +1,8 @@
 """The object branches of an eval-mode render on the device (objects.hip: nvfi_render_objects, k_select_fwd behind nvfi_render_fwd_select;
 TensorVMKeyframeTimeKplane.render_objects, Renderer.render_objects) against their float64 restatement (tests/objects64.py, pinned to the reference
-by tests/test_objects_golden.py), fields A and B with the fixture's MaskField (K = 8 and 3; K = 5: the first five rows of the K = 8 head).
+by tests/test_objects_golden.py), fields A and B with the fixture's MaskField (K = 8 and 3; K = 5: the first five rows of the K = 8 head; K = 9, 17
+and 32 on field A: the fixture's trunk under the heads of tests/maskfield64.py's params_for - from K = 9 on, accumulator registers 4..15 of the
+logit tile of k_mask_fwd and k_select_fwd carry live rows, from K = 17 on both half-waves hold rows >= 8).
 
 Layers: the yardstick is fed the DEVICE's own weight map, so the masked list is the same on both sides.  Bound per map, relative to max |map|:
 4 x the plain-fp32 floor of the case - objects64(float32) against objects64(float64) on the same weights, measured on the CPU, never below one fp32
@@ -28,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 
+import maskfield64 as m64
 import objects64 as o64
 import render64 as r64
 from conftest import GOLD
@@ -43,10 +46,15 @@ def fx():
     return np.load(os.path.join(GOLD, "objects.npz"))
 
 
+K_WIDE = (9, 17, 32)
+
+
 def _mask_field(sd, K):
     from nvfi_amd.models import MaskField
     mf = MaskField(n_layer=4, n_dim=128, input_dim=3, skips=[], mask_dim=K, mask_act="softmax")
     own = mf.state_dict()
+    if K > 8:       # the fixture's trunk under a head of maskfield64.params_for
+        sd = dict(sd, **{"mask_fc.weight": m64.params_for(K)[8], "mask_fc.bias": m64.params_for(K)[9]})
     for k, v in sd.items():
         own[k].copy_(torch.from_numpy(np.ascontiguousarray(v[:K] if k.startswith("mask_fc") else v)))
     return mf.cuda().eval()
@@ -59,7 +67,7 @@ def ctx(gold, fx):
         model, meta = make_model(kind)
         model.eval()
         sd = mask_state(fx, kind)
-        mfs = {K: _mask_field(sd, K) for K in ((8, 5) if kind == "A" else (3,))}
+        mfs = {K: _mask_field(sd, K) for K in ((8, 5) + K_WIDE if kind == "A" else (3,))}
         out[kind] = dict(model=model, f=model.nvfi, field=r64.Field(*field_state(model)), o=gold[f"{kind}:rays_o"], d=gold[f"{kind}:rays_d"],
                          white=bool(meta["white_background"]), mfs=mfs, K0=8 if kind == "A" else 3)
     yield out
@@ -138,6 +146,31 @@ def test_shapes(ctx, R, K):
     _check(c, _run(c, o, d, T_NONKEY, K=K), o, d, T_NONKEY, f"R{R}:K{K}", K=K)
     sel = np.linspace(0.0, 1.0, K).astype(np.float32)
     _check(c, _run(c, o, d, T_NONKEY, select=sel, K=K), o, d, T_NONKEY, f"R{R}:K{K}:select", select=sel, K=K)
+
+
+@pytest.mark.parametrize("K", K_WIDE)
+def test_more_than_eight_classes(ctx, K):
+    """field A, one non-keyframe time, R = 130: mask_map / obj_acc, the layers and the select render under the bounds of every other case.  The select
+    vectors: a ramp over all classes and, at K = 17 and 32, one that keeps only classes >= 16 - rows j and 16 + j of the logit tile sit in the same
+    register of the two half-waves, and a mix-up of the two in k_select_fwd would scale the density by the wrong classes' share"""
+    c = ctx["A"]
+    R = 130
+    idx = np.arange(R) % len(c["o"])
+    idx[-1] = 100
+    o, d = c["o"][idx], c["d"][idx]
+    assert c["mfs"][K].mask_fc.weight.shape == (K, 128)
+    y = _check(c, _run(c, o, d, T_NONKEY, K=K), o, d, T_NONKEY, f"R{R}:K{K}", K=K)
+    assert y["obj_acc"].shape == (R, K) and (np.abs(y["obj_acc"]).max(0) > 0).all(), "every class carries weight on some ray"
+    sels = [np.linspace(0.0, 1.0, K).astype(np.float32)]
+    if K > 16:
+        sels.append((np.arange(K) >= 16).astype(np.float32))
+    for i, sel in enumerate(sels):
+        ys = _check(c, _run(c, o, d, T_NONKEY, select=sel, K=K), o, d, T_NONKEY, f"R{R}:K{K}:select{i}", select=sel, K=K)
+        if i == 1:      # the yardstick itself tells the two halves apart: keeping rows j instead of 16 + j gives another weight map
+            swapped = np.zeros(K, np.float32)
+            swapped[:K - 16] = 1.0
+            other = o64.objects64(c["field"], _params(c, K), o, d, T_NONKEY, c["white"], select=swapped)
+            assert np.abs(other["weight"] - ys["weight"]).max() > 1e-3
 
 
 def test_rays_that_miss_the_box(ctx):
