@@ -441,6 +441,29 @@ int nvfi_density_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, floa
 int nvfi_app_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes);
 int nvfi_app_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, const float* view, float* rgb,
                 void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- differentiable field lookups (additions to ABI v5; csrc/lookup.hip): compute_densityfeature / compute_appfeature (tensorf_keyframe.py:233-310)
+ *      at given points as autograd carries them through the reference's plain torch code - to the six planes of the family, to basis_mat.weight
+ *      and to the points themselves, the time coordinate included.  xyzt (N,4): normalised x, y, z and t' (normalize_time_coord(t); per point,
+ *      fractional or outside [-1, 1]): every plane, time planes included, takes the four taps of F.grid_sample(align_corners=True,
+ *      padding_mode="zeros") on the cell common.h's bl_setup_xy picks from the fp32 coordinates, like nvfi_density_at.
+ *        density     feat = sum_c prod_i space_i[c] prod_i time_i[c]; the forward IS nvfi_density_at.
+ *        appearance  feat (N, app_dim) = basis_mat (prod_i space_i prod_i time_i).
+ *        g_feat      the upstream gradient d loss / d feat: (N) resp. (N, app_dim).
+ *        g_xyzt      (N,4), OVERWRITTEN (plain stores; may be NULL): d loss / d (x, y, z, t') - ATen's grid_sampler_2d_backward, the difference of the
+ *                    in-range taps times (W - 1) / 2, (H - 1) / 2 and, for t', (K - 1) / 2.  Repeats bit for bit, like feat.
+ *        grads       density: dps[3] / dpt[3]; appearance: aps[3] / apt[3] / basis.  ACCUMULATED (+=) into buffers the caller cleared; a NULL
+ *                    member (or grads == NULL) skips that tensor; no other member is read.  These are float atomics: they do NOT repeat bit for bit
+ *                    and are not covered by NVFI_DETERMINISTIC (2304 B of atomics per point for density, 4608 B for appearance).
+ *      The backward reads the taps again: no stash, no workspace, nothing is cleared, one launch on `stream`, no host wait - the calls can be
+ *      captured in a hipGraph.  A non-finite or far coordinate has every tap masked: value 0, gradients 0.  N == 0: nothing is launched or
+ *      written, 0 is returned.  Errors (2), before anything is launched: an unsupported descriptor, N >= 2^31 - 256 (chunk the points), a NULL
+ *      xyzt / g_feat / feat. */
+int nvfi_density_grad(const nvfi_field_desc* f, int64_t N, const float* xyzt /* (N,4) normalised x,y,z,t' */,
+                      const float* g_feat /* (N) */, float* g_xyzt /* (N,4), OVERWRITTEN, or NULL */,
+                      const nvfi_grads* grads /* dps[3], dpt[3] accumulate (+=); NULL pointers skipped */, void* stream);
+int nvfi_appfeat_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, float* feat /* (N, app_dim) */, void* stream);
+int nvfi_appfeat_grad(const nvfi_field_desc* f, int64_t N, const float* xyzt, const float* g_feat /* (N, app_dim) */,
+                      float* g_xyzt /* (N,4) or NULL */, const nvfi_grads* grads /* aps[3], apt[3], basis */, void* stream);
 /* renderModule(pts, viewdirs, features) as a stand-alone call - MLPRender_PE.forward (tensorf_base.py:88-98) or, with shading = 1,
  * SHRender (tensorf_model_utils.py:292-296): xyz (N,3) normalised positions, view (N,3), features (N, app_dim) -> rgb (N,3).
  * Workspace: 2 x nvfi_app_workspace_bytes(f, N), and less is refused (4).  Forward only (inside a render the module is differentiated by

@@ -74,6 +74,7 @@ EXPORTS = [
     "nvfi_advect_grad_workspace_bytes", "nvfi_advect_grad",
     "nvfi_ray_distortion_workspace_bytes", "nvfi_ray_distortion",
     "nvfi_flow_loss_workspace_bytes", "nvfi_flow_loss_fwd", "nvfi_flow_loss_bwd",
+    "nvfi_density_grad", "nvfi_appfeat_at", "nvfi_appfeat_grad",
 ]
 
 _LIB = None
@@ -112,6 +113,9 @@ def lib():
         L.nvfi_flow_loss_fwd.argtypes = [fp, C.c_int64, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp, fp, C.c_int, C.c_float,
                                          C.c_float, fp, C.c_int, fp, fp, fp, fp, C.c_int64, C.c_int64, fp, C.c_int64, fp]
         L.nvfi_flow_loss_bwd.argtypes = [fp, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, fp, fp, C.c_int64, fp]
+        L.nvfi_density_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
+        L.nvfi_appfeat_at.argtypes = [fp, C.c_int64, fp, fp, fp]
+        L.nvfi_appfeat_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
         _LIB = L
     return _LIB
 

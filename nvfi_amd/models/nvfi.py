@@ -55,6 +55,18 @@ class NVFi(nn.Module):
         """integrate_pos(pos, t, t_target) with gradients to `pos` and the velocity net (TensorVMKeyframeTimeKplane.advect)"""
         return self.nvfi.advect(pos, t, t_target, max_workspace_bytes=max_workspace_bytes)
 
+    def lookup_density(self, xyzt):
+        """compute_densityfeature with gradients to the points and the density planes (TensorVMKeyframeTimeKplane.lookup_density)"""
+        return self.nvfi.lookup_density(xyzt)
+
+    def lookup_appfeature(self, xyzt):
+        """compute_appfeature with gradients to the points, the appearance planes and basis_mat (TensorVMKeyframeTimeKplane.lookup_appfeature)"""
+        return self.nvfi.lookup_appfeature(xyzt)
+
+    def compute_appfeature(self, xyzt):
+        """compute_appfeature, forward only (TensorVMKeyframeTimeKplane.compute_appfeature)"""
+        return self.nvfi.compute_appfeature(xyzt)
+
     def distortion_delta(self):
         """stepSize / (far - near): the interval width the distortion loss takes (TensorVMKeyframeTimeKplane.distortion_delta)"""
         return self.nvfi.distortion_delta()

@@ -471,6 +471,64 @@ class _AdvectFn(torch.autograd.Function):
         return (None, gx, None, None, None) + tuple(grads)
 
 
+class _DensityLookupFn(torch.autograd.Function):
+    """autograd boundary around nvfi_density_at / nvfi_density_grad (include/nvfi_hip.h).  The forward IS field.compute_densityfeature and saves
+    only the points and the six density planes: the backward reads the taps again (no stash) and computes only what autograd asks for."""
+
+    @staticmethod
+    def forward(ctx, field, q, *planes):
+        feat = field.compute_densityfeature(q)
+        ctx.field = field
+        ctx.save_for_backward(q, *planes)
+        ctx.set_materialize_grads(False)
+        return feat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ..utils import field_lookup as fl
+        q, *planes = ctx.saved_tensors
+        if g is None:
+            return (None,) * (2 + len(planes))
+        field = ctx.field
+        desc = field._desc(list(planes) + field._render_params()[6:])
+        need = ctx.needs_input_grad[2:]
+        grads = _zero_grads(planes, need)          # the plain path of _AdvectFn.backward: fresh zero gradients, no arena, no side streams
+        gq = fl.density_grad_raw(desc, q, g, g_xyzt=True if ctx.needs_input_grad[1] else None,
+                                 grads=field._grads_struct(list(grads)) if any(need) else None)
+        return (None, gq) + tuple(grads)
+
+
+class _AppLookupFn(torch.autograd.Function):
+    """autograd boundary around nvfi_appfeat_at / nvfi_appfeat_grad (include/nvfi_hip.h): compute_appfeature with gradients to the points, the
+    six appearance planes and basis_mat.weight; built like _DensityLookupFn."""
+
+    @staticmethod
+    def forward(ctx, field, q, *params):
+        from ..utils import field_lookup as fl
+        feat = fl.appfeat_raw(field._desc(), q)
+        ctx.field = field
+        ctx.save_for_backward(q, *params)
+        ctx.set_materialize_grads(False)
+        return feat
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ..utils import field_lookup as fl
+        q, *params = ctx.saved_tensors
+        if g is None:
+            return (None,) * (2 + len(params))
+        field = ctx.field
+        rp = field._render_params()
+        desc = field._desc(rp[:6] + list(params) + rp[13:])
+        need = ctx.needs_input_grad[2:]
+        grads = _zero_grads(params, need)
+        gq = fl.appfeat_grad_raw(desc, q, g, g_xyzt=True if ctx.needs_input_grad[1] else None,
+                                 grads=field._grads_struct([None] * 6 + list(grads)) if any(need) else None)
+        return (None, gq) + tuple(grads)
+
+
 class _FlowLossFn(torch.autograd.Function):
     """autograd boundary around nvfi_flow_loss_fwd / nvfi_flow_loss_bwd (include/nvfi_hip.h), built like _AdvectFn: the forward runs behind the
     training render whose backward node `node` still holds its workspace and forms the value, d loss / d weights and the per-entry gradient at
@@ -1358,6 +1416,37 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         desc = self._desc()
         _lib.check(L.nvfi_density_at(C.byref(desc), C.c_int64(N), _lib.ptr(q), _lib.ptr(feat), _lib.ptr(sigma), _stream_ptr()))
         return feat.unsqueeze(-1)
+
+    def lookup_density(self, xyzt):
+        """compute_densityfeature WITH gradients (tensorf_keyframe.py:233-272 under autograd): (N,4) normalised (x,y,z,t') -> (N,1), differentiable
+        once to `xyzt` (all four columns) and to the six density planes - Lagrangian losses on advected points (`advect`), free-space / occupancy
+        losses from depth sensors, sparsity on random points, distillation.  sigma follows through feature2density (a torch softplus).  The value
+        is compute_densityfeature's bit for bit; under no_grad, or when neither `xyzt` nor a density plane requires grad, this IS that call.
+        The plane gradients are float atomics (not bit-repeatable); the gradient at `xyzt` repeats bit for bit."""
+        if not (isinstance(xyzt, torch.Tensor) and xyzt.is_cuda):
+            raise _lib.NvfiError("lookup_density needs its points on the GPU (no CPU fallback exists)")
+        planes = self._render_params()[:6]
+        if not (torch.is_grad_enabled() and (xyzt.requires_grad or any(p.requires_grad for p in planes))):
+            return self.compute_densityfeature(xyzt)
+        return _DensityLookupFn.apply(self, xyzt.reshape(-1, 4).contiguous().float(), *planes)
+
+    def lookup_appfeature(self, xyzt):
+        """compute_appfeature WITH gradients (tensorf_keyframe.py:274-310 under autograd): (N,4) -> (N, app_dim), differentiable once to `xyzt`, the
+        six appearance planes and basis_mat.weight.  renderModule on these features stays forward-only."""
+        if not (isinstance(xyzt, torch.Tensor) and xyzt.is_cuda):
+            raise _lib.NvfiError("lookup_appfeature needs its points on the GPU (no CPU fallback exists)")
+        params = self._render_params()[6:13]
+        if not (torch.is_grad_enabled() and (xyzt.requires_grad or any(p.requires_grad for p in params))):
+            return self.compute_appfeature(xyzt)
+        return _AppLookupFn.apply(self, xyzt.reshape(-1, 4).contiguous().float(), *params)
+
+    @torch.no_grad()
+    def compute_appfeature(self, xyzt):
+        """(N,4) normalised (x,y,z,t') -> (N, app_dim) (tensorf_keyframe.py:274-310); forward only, like compute_densityfeature."""
+        from ..utils import field_lookup as fl
+        if not (isinstance(xyzt, torch.Tensor) and xyzt.is_cuda):
+            raise _lib.NvfiError("compute_appfeature needs its points on the GPU (no CPU fallback exists)")
+        return fl.appfeat_raw(self._desc(), xyzt)
 
     @staticmethod
     @torch.no_grad()
