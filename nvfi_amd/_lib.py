@@ -3,6 +3,8 @@ a missing library or a non-GPU tensor raises."""
 import ctypes as C
 import os
 
+import torch
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.environ.get("NVFI_LIB", os.path.join(HERE, "csrc", "libnvfi_hip.so"))   # NVFI_LIB: alternative build (experiments)
 fp = C.c_void_p
@@ -125,6 +127,13 @@ def check(rc):
         raise NvfiError(f"libnvfi_hip error {rc}: {lib().nvfi_last_error().decode()}")
 
 
+def bytes_of(fn, *args):
+    """the int64 a size query of the library (nvfi_*_bytes) answers through its last argument"""
+    nb = C.c_int64(0)
+    check(fn(*args, C.byref(nb)))
+    return nb.value
+
+
 def capture_id(stream_handle):
     """id (> 0) of the hipGraph capture the stream takes part in, 0 when it is not capturing"""
     cid = C.c_uint64(0)
@@ -139,3 +148,24 @@ def ptr(t):
     if not t.is_cuda:
         raise NvfiError("NVFi HIP kernels need tensors on the GPU (no CPU fallback exists)")
     return C.c_void_p(t.data_ptr())
+
+
+def stream_ptr():
+    """handle of torch's current stream, as the `stream` argument of every library call"""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def plan_chunks(nbytes_of, cap, max_workspace_bytes, what, unit="entry"):
+    """(chunk, bytes, chunks) of a stash-bound adjoint over `cap` entries whose workspace for n entries at a time is nbytes_of(n): everything
+    at once when that fits max_workspace_bytes, else the largest multiple of 128 whose plan fits - found from an affine guess through the 128
+    and the 256 plan (the plans grow by whole 128-entry groups), stepped down while too large.  One group that does not fit is refused."""
+    chunk = cap
+    if nbytes_of(cap) > max_workspace_bytes:
+        b1, b2 = nbytes_of(128), nbytes_of(256)
+        if b1 > max_workspace_bytes:
+            raise NvfiError(f"{what}: max_workspace_bytes={max_workspace_bytes} is below the {b1} bytes one 128-{unit} group needs")
+        chunk = 128 * (1 + (max_workspace_bytes - b1) // max(b2 - b1, 1))
+        while chunk > 128 and nbytes_of(chunk) > max_workspace_bytes:
+            chunk -= 128
+        chunk = min(chunk, cap)
+    return chunk, nbytes_of(chunk), (cap + chunk - 1) // chunk if cap else 0

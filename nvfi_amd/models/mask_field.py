@@ -12,10 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .._lib import stream_ptr as _stream_ptr
 
 
 def _mask_desc(mf, params):
@@ -37,9 +34,8 @@ class _MaskFn(torch.autograd.Function):
         pts = point.detach().contiguous().float()
         params_c = [p.detach().contiguous() for p in params]
         md = _mask_desc(mf, params_c)
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_maskfield_workspace_bytes(C.byref(md), C.c_int64(N), C.c_int(1 if train else 0), C.byref(nbytes)))
-        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=pts.device)
+        nbytes = _lib.bytes_of(L.nvfi_maskfield_workspace_bytes, C.byref(md), C.c_int64(N), C.c_int(1 if train else 0))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
         out = torch.empty(N, mf.mask_dim, device=pts.device, dtype=torch.float32)
         mode = (1 if train else 0) | (2 if mf.mfma_fp16 else 0)
         _lib.check(L.nvfi_maskfield_fwd(C.byref(md), C.c_int64(N), _lib.ptr(pts), _lib.ptr(out), C.c_int(mode),

@@ -17,11 +17,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
+from .._lib import stream_ptr as _stream_ptr
+from . import field_slots as fs
+from .field_autograd import _AdvectFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _PdeFn, _RegFn, _RenderFn
+from .field_grads import FieldGrads, _rt, round64
+from .mask_field import _mask_desc
 from .tensorf_model_utils import AlphaGridMask
-
-# per-field runtime state that must not travel with copy.deepcopy / pickle of the module (HIP streams, events, pinned buffers, the
-# gradient arena): kept beside the module, keyed weakly
-_RUNTIME = weakref.WeakKeyDictionary()
+from .velocity_field import VelBasis, VelocityAABB, VelocityAABBSur
 
 # render_mse_backward_: the slots of the 64-float `loss` piece of its output buffer, one owner each
 _LOSS_MSE = 0                  # nvfi_render_fwd_mse
@@ -29,14 +31,6 @@ _LOSS_DEPTH = 1                # nvfi_depth_loss: the value ...
 _LOSS_DEPTH_COUNT = 2          # ... and its int64 count of the entries that took part (8-byte aligned: two floats)
 _LOSS_DISTORTION = 4           # nvfi_ray_distortion
 _LOSS_FLOW = 6                 # nvfi_flow_loss_fwd: the value and, in the next slot, n (the number of rays that counted)
-
-
-def _rt(field):
-    d = _RUNTIME.get(field)
-    if d is None:
-        d = _RUNTIME[field] = {}
-    return d
-from .velocity_field import VelBasis, VelocityAABB, VelocityAABBSur
 
 
 class MLPRender_PE(nn.Module):
@@ -87,493 +81,7 @@ def _cl(t):
     return t.contiguous(memory_format=torch.channels_last)
 
 
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class _RenderFn(torch.autograd.Function):
-    """autograd boundary around nvfi_render_fwd / nvfi_render_bwd (include/nvfi_hip.h)."""
-
-    @staticmethod
-    def forward(ctx, field, t, rays_o, rays_d, jitter, flags, *params):
-        L = _lib.lib()
-        R = rays_o.shape[0]
-        dev = rays_o.device
-        t_dev = getattr(t, "dev", None)        # DeviceTime: the kernels read the time from device memory; float(t) is the launch plan
-        t = float(t)
-        desc = field._desc()
-        S = desc.n_samples
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        rgb = torch.empty(R, 3, device=dev)
-        depth = torch.empty(R, device=dev)
-        acc = torch.empty(R, device=dev)
-        weights = torch.empty(R, S, device=dev)
-        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)      # all 8 entries are written by the call
-        _lib.check(L.nvfi_render_fwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(jitter),
-                                       C.c_float(t), _lib.ptr(t_dev), C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc),
-                                       _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), _stream_ptr()))
-        field.last_counters = counters
-        field._last_ws = ws if (flags & _lib.NVFI_WANT_MASK) else None
-        field._last_call = (R, t, flags)
-        if flags & _lib.NVFI_TRAIN:
-            ctx.field, ctx.t, ctx.flags, ctx.ws, ctx.t_on_device = field, t, flags, ws, t_dev is not None
-            ctx.vel_fp16 = int(desc.vel_fp16)      # the workspace layout depends on it: the backward plans with the forward's value
-            ctx.save_for_backward(rays_o, rays_d, weights, *params)
-        ctx.mark_non_differentiable(counters)
-        ctx.set_materialize_grads(False)     # unused outputs (depth, acc, the R x S weights) arrive as None, not as zero tensors
-        return rgb, depth, acc, weights, counters
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_depth, g_acc, g_weights, _gc):
-        L = _lib.lib()
-        rays_o, rays_d, weights, *params = ctx.saved_tensors
-        field = ctx.field
-        desc = field._desc(params)
-        desc.vel_fp16 = ctx.vel_fp16
-        need = ctx.needs_input_grad[6:]
-        inplace = field.accumulate_grads_inplace
-        if inplace == "arena":
-            # library-managed in-place accumulation (the default under a plain autograd driver): see _arena_attach
-            grads = field._arena_attach(field._render_params(), need)
-            inplace = grads is not None
-            if inplace:
-                field._wait_writers()
-                field._queue_join()
-        elif inplace:
-            # kernels accumulate (+=) straight into the parameters' .grad (e.g. views of one flat GradBucket buffer):
-            # no zero-fill, no AccumulateGrad add per tensor.  Autograd then sees "no gradient" for these inputs.
-            cur = field._render_params()
-            grads = []
-            for p, n in zip(cur, need):
-                if not n:
-                    grads.append(None)
-                    continue
-                if p.grad is None:
-                    p.grad = torch.zeros_like(p)
-                grads.append(p.grad)
-        if not inplace:
-            grads = _zero_grads(params, need)
-        G = field._grads_struct(grads)
-        gs = [None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_acc, g_weights)]
-        R = rays_o.shape[0]
-        _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(rays_o), _lib.ptr(rays_d), C.c_float(ctx.t), C.c_int(int(ctx.t_on_device)),
-                                     C.c_int(ctx.flags), _lib.ptr(weights), _lib.ptr(gs[0]), _lib.ptr(gs[1]), _lib.ptr(gs[2]),
-                                     _lib.ptr(gs[3]), C.byref(G), _lib.ptr(ctx.ws), C.c_int64(ctx.ws.numel()), _stream_ptr()))
-        ctx.ws = None
-        if inplace:
-            return (None,) * (6 + len(params))
-        return (None, None, None, None, None, None) + tuple(grads)
-
-
-def _zero_grads(params, need=None):
-    """Fresh zero gradients for `params` (None where `need` is false) as views of ONE zero-filled buffer: one fill launch per backward
-    node instead of one per parameter (the plain-autograd path of the reference's training loop is bound by the host's launch rate)."""
-    need = [True] * len(params) if need is None else list(need)
-    offs, total = [], 0
-    for p, n in zip(params, need):
-        offs.append(total)
-        if n:
-            total += (p.numel() + 63) // 64 * 64      # 256-byte aligned views (the plane-gradient kernels use 16-byte accesses)
-    if total == 0:
-        return [None] * len(params)
-    ref = next(p for p, n in zip(params, need) if n)
-    flat = torch.zeros(total, dtype=ref.dtype, device=ref.device)
-    # same strides as the parameter (the planes are stored channel-last under an NCHW shape; all parameters are dense)
-    return [flat[o:o + p.numel()].as_strided(p.shape, p.stride()) if n else None for p, n, o in zip(params, need, offs)]
-
-
-class _PdeFn(torch.autograd.Function):
-    """nvfi_pde_loss computes the loss AND its parameter gradients in one pass; backward scales them."""
-
-    @staticmethod
-    def forward(ctx, field, points, t, *params):
-        L = _lib.lib()
-        dev = points.device
-        P = points.shape[0]
-        desc = field._desc()
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_pde_workspace_bytes(C.byref(desc), C.c_int64(P), C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        out = torch.zeros(4, device=dev)
-        grads = _zero_grads(params)
-        G = field._grads_struct_vel(grads)
-        counters = torch.zeros(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
-        kept = torch.zeros(P, dtype=torch.uint8, device=dev) if field.pde_debug else None
-        jac = torch.zeros(field.pde_debug, 6, 4, device=dev) if field.pde_debug else None
-        info = (C.c_int64 * 2)()
-        # split call (field.pde_split, default on): the VALUE is complete on the current stream after the Jacobian forward, the adjoint pass and
-        # the weight gradients run on the field's PDE side stream - under the reference's loop, which waits for the value right after this call
-        # (train_nvfi.py:233) and then differentiates the renders, the PDE adjoint overlaps with them; backward() waits for `ctx.done`
-        side = field._side_stream("p") if field.pde_split else None
-        _lib.check(L.nvfi_pde_loss_split(C.byref(desc), C.c_int64(P), _lib.ptr(points), _lib.ptr(t), C.c_float(1.0), _lib.ptr(out),
-                                         C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters),
-                                         _lib.ptr(kept), _lib.ptr(jac), C.c_int64(int(field.pde_debug)), info, _stream_ptr(),
-                                         C.c_void_p(side.cuda_stream) if side is not None else None))
-        ctx.done = None
-        if side is not None:
-            ctx.done = torch.cuda.Event()
-            ctx.done.record(side)
-            ws.record_stream(side)
-            grads[0]._base.record_stream(side)
-        field.last_pde_kept, field.last_pde_jac = kept, jac
-        field.last_pde_n_kept = int(info[0])
-        field.last_pde_out = out
-        field.last_pde_counters = counters
-        ctx.save_for_backward(grads[0]._base)            # the one flat buffer behind the views
-        ctx.shapes = [(p.shape, p.stride()) for p in params]
-        ctx.field = field
-        return out[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        field = ctx.field
-        if ctx.done is not None:
-            torch.cuda.current_stream().wait_event(ctx.done)     # the adjoint half of the split call has filled the gradients
-        if field.accumulate_grads_inplace == "arena":
-            tail = field._arena_attach(field._pde_params(), [True] * 24, want_tail=True)
-            if tail is not None and tail.numel() == ctx.saved_tensors[0].numel():
-                # one launch: arena[velocity nets] += g * (gradients of the un-weighted loss); a plain read-modify-write, so the
-                # backward kernels of the renders (atomic adds from other streams) are ordered behind it (_note_writer)
-                field._wait_writers(True)
-                tail.addcmul_(ctx.saved_tensors[0], g.to(tail.dtype).expand_as(tail))
-                field._note_writer()
-                field._queue_join()
-                return (None,) * (3 + len(ctx.shapes))
-        flat = ctx.saved_tensors[0] * g                  # one launch for all 24 tensors
-        out, o = [], 0
-        for shp, strides in ctx.shapes:
-            n = shp.numel()
-            out.append(flat[o:o + n].as_strided(shp, strides))
-            o += (n + 63) // 64 * 64
-        return (None, None, None) + tuple(out)
-
-
-class _RegFn(torch.autograd.Function):
-    """`density_L1()` / `TV_loss_density(reg)` / `TV_loss_app(reg)` of the reference (tensorf_keyframe.py:188-231) on nvfi_plane_regs (regs.hip)
-    instead of ~230 torch launches each.  The kernel computes all three values in one pass over the planes, and a driver calls all three per
-    iteration (train_nvfi.py:203-217), so:
-      forward   the first call of an iteration runs the pass and keeps the value triple; the next two find the planes unchanged (same tensors,
-                same `_version`, no fused-Adam step since) and return their entry of it - one pass instead of three;
-      backward  with in-place gradient accumulation (arena / caller-owned .grad) the three nodes only deposit their upstream weights; the last
-                one - or the engine's end-of-backward callback, if the graph held fewer - runs ONE gradient pass with all of them
-                (nvfi_plane_regs_dev: weights read from device memory, no host sync).  Under pure autograd each node has to hand its own
-                gradients back to the engine, so each runs its own pass as before."""
-
-    @staticmethod
-    def forward(ctx, field, which, *planes):
-        L = _lib.lib()
-        rt = _rt(field)
-        from .. import optim as _optim
-        # nvfi_amd.optim.Adam moves the planes through raw pointers (no `_version` bump): its generation counter is part of the key, as in _frags
-        key = (tuple((p.data_ptr(), p._version) for p in planes), _optim.GENERATION)
-        c = rt.get("_reg_fwd")
-        if c is None or c[0] != key:
-            # a new pass = a new iteration: whatever an aborted backward of the previous one left behind (deposited weights, a live count that
-            # never reached zero because its graph was dropped) must not leak into this one's single gradient pass (ADVICE r4)
-            rt.pop("_reg_pending", None)
-            rt["_reg_live"] = 0
-            out = torch.empty(3, device=planes[0].device)
-            desc = field._desc()
-            _lib.check(L.nvfi_plane_regs(C.byref(desc), C.c_float(0.0), C.c_float(0.0), C.c_float(0.0), _lib.ptr(out), None, _stream_ptr()))
-            c = (key, out, torch.cuda.current_stream())
-            rt["_reg_fwd"] = c
-        elif c[2] != torch.cuda.current_stream():
-            torch.cuda.current_stream().wait_stream(c[2])
-        ctx.field, ctx.which = field, which
-        ctx.save_for_backward(*planes)
-        if any(ctx.needs_input_grad):
-            rt["_reg_live"] = rt.get("_reg_live", 0) + 1
-        return c[1][which].clone()
-
-    @staticmethod
-    def _flush(field):
-        """one gradient pass for every deposited weight (in-place modes)"""
-        rt = _rt(field)
-        pend = rt.pop("_reg_pending", None)
-        rt["_reg_live"] = 0
-        if not pend:
-            return
-        L = _lib.lib()
-        planes, ws = pend["planes"], pend["w"]
-        touched = set()
-        for which in ws:
-            touched |= set((0, 1, 2, 3, 4, 5) if which < 2 else (6, 7, 8))
-        inplace = field.accumulate_grads_inplace
-        cur = field._render_params()[:9]
-        grads = [None] * 9
-        arena = False
-        if inplace == "arena":
-            ag = field._arena_attach(field._render_params(), [k in touched for k in range(9)] + [False] * 22)
-            arena = ag is not None
-            if arena:
-                grads = ag[:9]
-                field._wait_writers(True)      # k_plane_regs adds with plain read-modify-writes: not next to another stream's kernels
-                field._queue_join()
-        if not arena:
-            for k in touched:
-                if cur[k].grad is None:
-                    cur[k].grad = torch.zeros_like(cur[k])
-                grads[k] = cur[k].grad
-        G = field._grads_struct(grads + [None] * 22)
-        dev = planes[0].device
-        zero = None
-        parts = []
-        for which in range(3):
-            if which in ws:
-                parts.append(ws[which].reshape(1).to(torch.float32))
-            else:
-                zero = torch.zeros(1, device=dev) if zero is None else zero
-                parts.append(zero)
-        w3 = torch.cat(parts)
-        out = torch.empty(3, device=dev)
-        desc = field._desc(list(planes) + field._render_params()[9:])
-        _lib.check(L.nvfi_plane_regs_dev(C.byref(desc), _lib.ptr(w3), _lib.ptr(out), C.byref(G), _stream_ptr()))
-        if arena:
-            field._note_writer()
-
-    @staticmethod
-    def backward(ctx, g):
-        L = _lib.lib()
-        field, which = ctx.field, ctx.which
-        planes = ctx.saved_tensors                      # the 9 regularised planes: dps[3], dpt[3], aps[3]
-        rt = _rt(field)
-        rt["_reg_live"] = max(rt.get("_reg_live", 1) - 1, 0)
-        rt.pop("_reg_fwd", None)       # the value triple is shared by the calls of ONE iteration only (a driver that never moves the planes - bench.py's
-                                        # stationary mode - must not skip next iteration's pass)
-        inplace = field.accumulate_grads_inplace
-        if inplace:
-            # deposit; the last live node (or the end of this backward pass) runs the single gradient pass.  A field with autograd hooks on a
-            # parameter gets pure autograd from _arena_attach -> the per-node path below
-            hooked = inplace == "arena" and any(p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None) for p in field._arena_params())
-            if not hooked:
-                pend = rt.get("_reg_pending")
-                if pend is None:
-                    pend = rt["_reg_pending"] = dict(planes=planes, w={})
-                    ref = weakref.ref(field)
-                    torch.autograd.Variable._execution_engine.queue_callback(lambda: ref() is not None and _RegFn._flush(ref()))
-                pend["w"][which] = g if which not in pend["w"] else pend["w"][which] + g
-                if rt["_reg_live"] == 0:
-                    _RegFn._flush(field)
-                return (None, None) + (None,) * 9
-        touched = (0, 1, 2, 3, 4, 5) if which < 2 else (6, 7, 8)
-        grads = _zero_grads(planes, [k in touched for k in range(9)])
-        G = field._grads_struct(grads + [None] * 22)
-        w3 = torch.zeros(3, device=g.device)
-        w3[which] = g
-        out = torch.empty(3, device=g.device)
-        desc = field._desc(list(planes) + field._render_params()[9:])
-        _lib.check(L.nvfi_plane_regs_dev(C.byref(desc), _lib.ptr(w3), _lib.ptr(out), C.byref(G), _stream_ptr()))
-        return (None, None) + tuple(grads)
-
-
-class _CharFn(torch.autograd.Function):
-    """nvfi_char_loss computes the value AND the unit-weight gradients of its 13 tensors (twelve planes, basis_mat) in one pass, into a private
-    buffer; backward scales them by the upstream gradient (the pattern of _PdeFn)."""
-
-    @staticmethod
-    def forward(ctx, field, points, t, *params):
-        need = ctx.needs_input_grad[3:]
-        grads = _zero_grads(params, need) if any(need) else [None] * len(params)
-        terms, points0 = field._char_call(points, t, 1.0, grads if any(need) else None, params)
-        flat = next((g._base for g in grads if g is not None), None)
-        if flat is not None:
-            ctx.save_for_backward(flat)
-        ctx.field, ctx.need = field, list(need)
-        ctx.shapes = [(p.shape, p.stride()) for p in params]
-        ctx.mark_non_differentiable(terms, points0)
-        return terms[0] + terms[1], terms, points0
-
-    @staticmethod
-    def backward(ctx, g, _gt, _gp):
-        if not ctx.saved_tensors:
-            return (None,) * (3 + len(ctx.shapes))
-        field, saved = ctx.field, ctx.saved_tensors[0]
-        if field.accumulate_grads_inplace == "arena" and all(ctx.need):
-            params = field._render_params()[:13]
-            tgt = field._arena_attach(params, ctx.need)
-            a = _rt(field).get("_arena")
-            if tgt is not None and a is not None and all(x is y for x, y in zip(a["params"][:13], params)) and all(p.grad is a["views"].get(id(p)) for p in params):
-                # one launch: arena[planes, basis_mat] += g * (unit-weight gradients); a plain read-modify-write, so it is ordered against the
-                # atomic adds of the render backward on the field's side streams (_wait_writers / _note_writer), like _PdeFn's
-                field._wait_writers(True)
-                head = a["flat"][:saved.numel()]
-                head.addcmul_(saved, g.to(head.dtype).expand_as(head))
-                field._note_writer()
-                field._queue_join()
-                return (None,) * (3 + len(ctx.shapes))
-        flat = saved * g
-        out, o = [], 0
-        for (shp, strides), n in zip(ctx.shapes, ctx.need):
-            if not n:
-                out.append(None)
-                continue
-            k = shp.numel()
-            out.append(flat[o:o + k].as_strided(shp, strides))
-            o += (k + 63) // 64 * 64
-        return (None, None, None) + tuple(out)
-
-
-class _AdvectFn(torch.autograd.Function):
-    """autograd boundary around nvfi_integrate_pos / nvfi_advect_grad (include/nvfi_hip.h) for host-scalar times.  The forward IS
-    field.integrate_pos and saves only the positions: the backward runs the warp again in training form, chunk by chunk on one workspace of at
-    most `max_ws` bytes (the stash is ~10.8 KB per point and RK2 step), and accumulates the net's gradients over the chunks."""
-
-    @staticmethod
-    def forward(ctx, field, x, t, t_target, max_ws, *params):
-        tt = torch.full((x.shape[0],), t, dtype=torch.float32, device=x.device)
-        bb = torch.full((x.shape[0],), t_target, dtype=torch.float32, device=x.device)
-        xk = field.integrate_pos(x, tt, bb)
-        ctx.field, ctx.t, ctx.t_target, ctx.max_ws = field, t, t_target, int(max_ws)
-        ctx.save_for_backward(x, *params)
-        ctx.set_materialize_grads(False)
-        return xk
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        x, *params = ctx.saved_tensors
-        if g is None:
-            return (None,) * (5 + len(params))
-        L = _lib.lib()
-        field = ctx.field
-        desc = field._desc(field._render_params()[:19] + list(params))
-        need = ctx.needs_input_grad[5:]
-        grads = _zero_grads(params, need)          # the plain path of _RenderFn.backward: fresh zero gradients, no arena, no side streams
-        G = field._grads_struct_vel(list(grads) + [None] * 12)
-        g = g.reshape(-1, 3).contiguous().float()
-        N = x.shape[0]
-        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        t, t1 = C.c_float(ctx.t), C.c_float(ctx.t_target)
-
-        def nbytes(n):
-            nb = C.c_int64(0)
-            _lib.check(L.nvfi_advect_grad_workspace_bytes(C.byref(desc), C.c_int64(n), t, t1, C.byref(nb)))
-            return nb.value
-
-        chunk = N
-        if nbytes(N) > ctx.max_ws:
-            # the plan is affine in the number of whole 128-point groups: the largest multiple of 128 that fits
-            b1, b2 = nbytes(128), nbytes(256)
-            if b1 > ctx.max_ws:
-                raise _lib.NvfiError(f"advect: max_workspace_bytes={ctx.max_ws} is below the {b1} bytes one 128-point group needs")
-            chunk = 128 * (1 + (ctx.max_ws - b1) // (b2 - b1))
-            while chunk > 128 and nbytes(chunk) > ctx.max_ws:
-                chunk -= 128
-        ws = torch.empty(nbytes(min(chunk, N)), dtype=torch.uint8, device=x.device)
-        field.last_advect_chunks = (N + chunk - 1) // chunk if N else 0
-        field.last_advect_workspace_bytes = ws.numel()
-        for i in range(0, N, chunk):
-            n = min(chunk, N - i)
-            _lib.check(L.nvfi_advect_grad(C.byref(desc), C.c_int64(n), _lib.ptr(x[i:i + n]), t, t1, _lib.ptr(g[i:i + n]),
-                                          None if gx is None else _lib.ptr(gx[i:i + n]), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
-        return (None, gx, None, None, None) + tuple(grads)
-
-
-class _DensityLookupFn(torch.autograd.Function):
-    """autograd boundary around nvfi_density_at / nvfi_density_grad (include/nvfi_hip.h).  The forward IS field.compute_densityfeature and saves
-    only the points and the six density planes: the backward reads the taps again (no stash) and computes only what autograd asks for."""
-
-    @staticmethod
-    def forward(ctx, field, q, *planes):
-        feat = field.compute_densityfeature(q)
-        ctx.field = field
-        ctx.save_for_backward(q, *planes)
-        ctx.set_materialize_grads(False)
-        return feat
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        from ..utils import field_lookup as fl
-        q, *planes = ctx.saved_tensors
-        if g is None:
-            return (None,) * (2 + len(planes))
-        field = ctx.field
-        desc = field._desc(list(planes) + field._render_params()[6:])
-        need = ctx.needs_input_grad[2:]
-        grads = _zero_grads(planes, need)          # the plain path of _AdvectFn.backward: fresh zero gradients, no arena, no side streams
-        gq = fl.density_grad_raw(desc, q, g, g_xyzt=True if ctx.needs_input_grad[1] else None,
-                                 grads=field._grads_struct(list(grads)) if any(need) else None)
-        return (None, gq) + tuple(grads)
-
-
-class _AppLookupFn(torch.autograd.Function):
-    """autograd boundary around nvfi_appfeat_at / nvfi_appfeat_grad (include/nvfi_hip.h): compute_appfeature with gradients to the points, the
-    six appearance planes and basis_mat.weight; built like _DensityLookupFn."""
-
-    @staticmethod
-    def forward(ctx, field, q, *params):
-        from ..utils import field_lookup as fl
-        feat = fl.appfeat_raw(field._desc(), q)
-        ctx.field = field
-        ctx.save_for_backward(q, *params)
-        ctx.set_materialize_grads(False)
-        return feat
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        from ..utils import field_lookup as fl
-        q, *params = ctx.saved_tensors
-        if g is None:
-            return (None,) * (2 + len(params))
-        field = ctx.field
-        rp = field._render_params()
-        desc = field._desc(rp[:6] + list(params) + rp[13:])
-        need = ctx.needs_input_grad[2:]
-        grads = _zero_grads(params, need)
-        gq = fl.appfeat_grad_raw(desc, q, g, g_xyzt=True if ctx.needs_input_grad[1] else None,
-                                 grads=field._grads_struct([None] * 6 + list(grads)) if any(need) else None)
-        return (None, gq) + tuple(grads)
-
-
-class _FlowLossFn(torch.autograd.Function):
-    """autograd boundary around nvfi_flow_loss_fwd / nvfi_flow_loss_bwd (include/nvfi_hip.h), built like _AdvectFn: the forward runs behind the
-    training render whose backward node `node` still holds its workspace and forms the value, d loss / d weights and the per-entry gradient at
-    the displaced points in the call's own workspace; the backward runs the adjoint of integrate_pos chunk by chunk on that workspace and hands
-    d loss / d weights to autograd, which carries it into _RenderFn.backward as g_weights."""
-
-    @staticmethod
-    def forward(ctx, field, weights, node, dt, camera, target, valid, kind, huber_delta, max_ws, *params):
-        from ..utils import flow_loss as fl
-        rays_o, rays_d, w_saved = node.saved_tensors[:3]
-        desc = field._desc(field._render_params()[:19] + list(params))
-        desc.vel_fp16 = node.vel_fp16
-        want_gw = ctx.needs_input_grad[1]
-        call = fl.flow_loss_raw(desc, node.ws, node.flags, rays_o, rays_d, w_saved, node.t, dt, camera, target, valid=valid, kind=kind,
-                                huber_delta=huber_delta, g_weights=None if want_gw else False, max_workspace_bytes=max_ws)
-        field.last_flow_chunks, field.last_flow_workspace_bytes = call["chunks"], call["workspace"].numel()
-        field.last_flow2d, field.last_flow_n = call["flow2d"], call["loss"][1]
-        ctx.field, ctx.call, ctx.vel_fp16 = field, call, node.vel_fp16
-        ctx.save_for_backward(*params)
-        return call["loss"][0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        from ..utils import flow_loss as fl
-        params = list(ctx.saved_tensors)
-        field, call = ctx.field, ctx.call
-        if call is None:
-            raise ValueError("flow_loss: the workspace of this call was released by its first backward; a second backward needs a new flow_loss call")
-        desc = field._desc(field._render_params()[:19] + params)
-        desc.vel_fp16 = ctx.vel_fp16
-        need = ctx.needs_input_grad[10:]
-        grads = _zero_grads(params, need)          # the plain path of _AdvectFn.backward: fresh zero gradients, no arena, no side streams
-        if any(need):
-            fl.flow_loss_backward_raw(desc, call, field._grads_struct_vel(list(grads) + [None] * 12))
-        g = g.detach().float()
-        for gr in grads:                           # the upstream gradient never visits the host
-            if gr is not None:
-                gr.mul_(g)
-        g_w = call["g_weights"] * g if ctx.needs_input_grad[1] else None
-        ctx.call = None
-        return (None, g_w) + (None,) * 8 + tuple(grads)
-
-
-class TensorVMKeyframeTimeKplane(nn.Module):
+class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
     def __init__(self, aabb, gridSize, device, near_far, cfg):
         super().__init__()
         self.matModeSpace = [[0, 1], [0, 2], [1, 2]]
@@ -742,7 +250,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         ps = list(self.density_plane_space) + list(self.density_plane_time) + list(self.app_plane_space) + list(self.app_plane_time)
         ps.append(self.basis_mat.weight)
         if self.shadingMode == "SH":
-            ps += [None] * 6                      # no render MLP: the six slots stay empty so that the velocity slots keep their index
+            ps += [None] * (fs.RENDER_MLP.stop - fs.RENDER_MLP.start)      # no render MLP: the six slots stay empty so that the velocity slots keep their index
         else:
             for i in (0, 2, 4):
                 ps += [self.renderModule.mlp[i].weight, self.renderModule.mlp[i].bias]
@@ -808,7 +316,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         (ABI v5) points at the field's fragment cache when that is current for these weights (_frags)."""
         ps = self._render_params() if params is None else list(params)
         pp = self._pde_params() if self.use_vel else []
-        key = (tuple(0 if p is None else p.data_ptr() for p in ps), tuple(p.data_ptr() for p in pp[12:]), self._host_state())
+        key = (tuple(0 if p is None else p.data_ptr() for p in ps), tuple(p.data_ptr() for p in pp[fs.PDE_A_WEIGHT_NET]), self._host_state())
         rt = _rt(self)
         c = rt.get("_desc_cache")
         if c is None or c[0] != key:
@@ -840,20 +348,12 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         d.step_size = self._step_host
         d.density_shift, d.distance_scale = float(self.density_shift), float(self.distance_scale)
         d.weight_thres, d.alpha_thres, d.tmax = float(self.rayMarch_weight_thres), float(self.alphaMask_thres), float(self.tmax)
-        for p in ps[:12]:
+        for p in ps[fs.FACTOR_PLANES]:
             if not p.is_contiguous(memory_format=torch.channels_last):
                 raise _lib.NvfiError("factor planes must be channels_last (call field._fix_layout())")
-        for i in range(3):
-            d.dps[i] = _lib.ptr(ps[i]); d.dpt[i] = _lib.ptr(ps[3 + i]); d.aps[i] = _lib.ptr(ps[6 + i]); d.apt[i] = _lib.ptr(ps[9 + i])
-        d.basis = _lib.ptr(ps[12])
-        for i in range(3):
-            d.rW[i] = _lib.ptr(ps[13 + 2 * i]); d.rb[i] = _lib.ptr(ps[14 + 2 * i])
+        fs.fill(d, ps)
         if self.use_vel:
-            if len(ps) >= 31:
-                for i in range(6):
-                    d.vW[i] = _lib.ptr(ps[19 + 2 * i]); d.vb[i] = _lib.ptr(ps[20 + 2 * i])
-            for i in range(6):
-                d.aW[i] = _lib.ptr(pp[12 + 2 * i]); d.ab[i] = _lib.ptr(pp[13 + 2 * i])
+            fs.fill(d, pp, fs.PDE_A_MEMBERS)
         if self.alphaMask is not None:
             d.has_amask = 1
             v = self.alphaMask.alpha_volume
@@ -876,7 +376,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         if not on or not ps[0].is_cuda:
             return None
         from .. import optim as _optim
-        lin = [p for p in ps[12:] if p is not None] + list(pp[12:])
+        lin = [p for p in ps[fs.LINEARS] if p is not None] + list(pp[fs.PDE_A_WEIGHT_NET])
         key = (tuple(p.data_ptr() for p in lin), tuple(p._version for p in lin), _optim.GENERATION, rt.get("_frag_epoch", 0))
         fc = rt.get("_frag_cache")
         cur = torch.cuda.current_stream()
@@ -896,9 +396,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             L = _lib.lib()
             buf = fc["buf"] if fc is not None and fc["buf"].device == ps[0].device else None
             if buf is None:
-                nb = C.c_int64(0)
-                _lib.check(L.nvfi_frag_cache_bytes(C.byref(d), C.byref(nb)))
-                buf = torch.empty(nb.value, dtype=torch.uint8, device=ps[0].device)
+                nb = _lib.bytes_of(L.nvfi_frag_cache_bytes, C.byref(d))
+                buf = torch.empty(nb, dtype=torch.uint8, device=ps[0].device)
             d.frags = None
             _lib.check(L.nvfi_pack_frags(C.byref(d), _lib.ptr(buf), C.c_int64(buf.numel()), C.c_void_p(cur.cuda_stream)))
             ev = torch.cuda.Event()
@@ -913,13 +412,11 @@ class TensorVMKeyframeTimeKplane(nn.Module):
     def render_workspace_bytes(self, R, t, train=False, transfer=False, flow=False, objects=False):
         """bytes nvfi_render_fwd[_t] plans for R rays at time t (include/nvfi_hip.h: nvfi_render_workspace_bytes_t); flow: with the room
         nvfi_render_flow needs (render_flow); objects: with the mask branch's and nvfi_render_fwd_select's room (render_objects)"""
-        nb = C.c_int64(0)
         desc = self._desc()
         flags = (_lib.NVFI_TRAIN if train else 0) | (_lib.NVFI_TRANSFER if transfer else 0) | (_lib.NVFI_WANT_FLOW if flow else 0)
         if objects:
             flags |= _lib.NVFI_WANT_MASK | _lib.NVFI_WANT_SELECT
-        _lib.check(_lib.lib().nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(int(R)), C.c_int(flags), C.c_float(float(t)), C.byref(nb)))
-        return int(nb.value)
+        return _lib.bytes_of(_lib.lib().nvfi_render_workspace_bytes_t, C.byref(desc), C.c_int64(int(R)), C.c_int(flags), C.c_float(float(t)))
 
     def invalidate_frags(self):
         """the weights were edited behind torch's version counters (p.data.copy_(), a raw kernel): the next call repacks"""
@@ -944,158 +441,54 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         whose pack launch is not a node of its own capture."""
         _rt(self)["_frag_trust_graph"] = bool(on)
 
+    def _params_with(self, group, tensors):
+        """the current 31-list with the slots of `group` (a slice of field_slots) replaced by `tensors`, e.g. the ones autograd saved"""
+        ps, tensors = self._render_params(), list(tensors)
+        if len(ps[group]) != len(tensors):
+            raise ValueError(f"{len(tensors)} tensors for the {len(ps[group])} slots of {group}")
+        ps[group] = tensors
+        return ps
+
     def _grads_struct(self, grads):
-        G = _lib.Grads()
-        g = list(grads) + [None] * (31 - len(grads))
-        for i in range(3):
-            G.dps[i] = _lib.ptr(g[i]); G.dpt[i] = _lib.ptr(g[3 + i]); G.aps[i] = _lib.ptr(g[6 + i]); G.apt[i] = _lib.ptr(g[9 + i])
-        G.basis = _lib.ptr(g[12])
-        for i in range(3):
-            G.rW[i] = _lib.ptr(g[13 + 2 * i]); G.rb[i] = _lib.ptr(g[14 + 2 * i])
-        for i in range(6):
-            G.vW[i] = _lib.ptr(g[19 + 2 * i]); G.vb[i] = _lib.ptr(g[20 + 2 * i])
-        return G
+        """nvfi_grads over gradient tensors in _render_params() order (a shorter list leaves NULL behind it)"""
+        return fs.fill(_lib.Grads(), grads)
 
     def _grads_struct_vel(self, grads):
-        G = _lib.Grads()
-        for i in range(6):
-            G.vW[i] = _lib.ptr(grads[2 * i]); G.vb[i] = _lib.ptr(grads[2 * i + 1])
-            G.aW[i] = _lib.ptr(grads[12 + 2 * i]); G.ab[i] = _lib.ptr(grads[13 + 2 * i])
-        return G
-
-    # ------------------------------------------------------------------ gradient arena + side streams (plain-autograd drivers)
-    def _arena_params(self):
-        ps = self._render_params()
-        if self.use_vel:
-            ps = ps + self._pde_params()[12:]           # + the acceleration net: the PDE parameters are then the last 24 entries
-        return [p for p in ps if p is not None]
-
-    def _arena_attach(self, params, need, want_tail=False):
-        """Gradient targets for `params` (None where `need` is false) as views of the field's persistent flat buffer.  A parameter whose
-        .grad is None gets its (zeroed) view attached; when that is true for every parameter of the field - the state a driver's
-        `zero_grad(set_to_none=True)` leaves behind - the whole buffer is cleared with ONE fill.  A .grad the caller put there is used
-        as it is when its layout matches the parameter's; otherwise None is returned and the call falls back to pure autograd.
-        want_tail: return the flat view that covers the 24 velocity-net tensors instead (they are contiguous at the end)."""
-        ps = self._arena_params()
-        # a hook on any parameter (tensor hooks, post-accumulate-grad hooks: DDP, optimiser-in-backward, clipping) only fires when the
-        # engine itself accumulates the gradient: such a field gets pure autograd
-        for p in ps:
-            if p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None):
-                return None
-        key = tuple((id(p), tuple(p.shape), p.stride()) for p in ps)
-        a = _rt(self).get("_arena")
-        if a is None or a["key"] != key or a["flat"].device != ps[0].device:
-            offs, total = [], 0
-            for p in ps:
-                offs.append(total)
-                total += (p.numel() + 63) // 64 * 64          # 256-byte aligned views, same packing as _zero_grads
-            flat = torch.zeros(total, dtype=torch.float32, device=ps[0].device)
-            views = {id(p): flat[o:o + p.numel()].as_strided(p.shape, p.stride()) for p, o in zip(ps, offs)}
-            a = dict(key=key, flat=flat, views=views, offs=offs, params=ps, event=None, tail=flat[offs[-24]:] if (self.use_vel and len(ps) >= 24) else None)
-            _rt(self)["_arena"] = a
-        # only the parameters THIS node differentiates are attached: a parameter no term of the loss reaches keeps .grad = None and the
-        # optimiser skips it, exactly as under pure autograd
-        wanted = {id(p) for p, n in zip(params, need) if n and p is not None}
-        idx = [i for i, p in enumerate(a["params"]) if id(p) in wanted and p.requires_grad and p.grad is None]
-        if a["event"] is not None:
-            torch.cuda.current_stream().wait_event(a["event"])      # fills queued by nodes that ran on other streams
-        if idx:
-            lo, hi = idx[0], idx[-1]
-            with torch.no_grad():
-                if len(idx) == hi - lo + 1:        # a contiguous run of the buffer (the usual case): ONE fill
-                    end = a["offs"][hi + 1] if hi + 1 < len(a["offs"]) else a["flat"].numel()
-                    a["flat"][a["offs"][lo]:end].zero_()
-                else:
-                    for i in idx:
-                        a["views"][id(a["params"][i])].zero_()
-            for i in idx:
-                p = a["params"][i]
-                p.grad = a["views"][id(p)]
-            ev = torch.cuda.Event()
-            ev.record()
-            a["event"] = ev            # other streams' backward nodes order themselves behind the fill
-        out = []
-        for p, n in zip(params, need):
-            if not n or p is None:
-                out.append(None)
-                continue
-            g = p.grad
-            if g is None or g.stride() != p.stride() or g.dtype != torch.float32 or g.device != p.device:
-                return None
-            out.append(g)
-        if want_tail:
-            vs = self._pde_params()
-            ok = a["tail"] is not None and all(p.grad is a["views"].get(id(p)) for p in vs)
-            return a["tail"] if ok else None
-        return out
-
-    def _side_stream(self, kind):
-        pool = _rt(self).get("_side_pool")
-        if pool is None:
-            dev = self.aabb.device
-            pool = dict(r=[torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)], p=torch.cuda.Stream(device=dev), k=0)
-            _rt(self)["_side_pool"] = pool
-        if kind == "p":
-            return pool["p"]
-        pool["k"] += 1
-        return pool["r"][pool["k"] & 1]
-
-    def _use_side_streams(self):
-        return (self.auto_overlap and self.accumulate_grads_inplace == "arena" and self.aabb.is_cuda and torch.is_grad_enabled()
-                and not torch.cuda.is_current_stream_capturing())
-
-    def _note_writer(self):
-        """The current stream just queued a non-atomic read-modify-write of gradient memory: later backward nodes (any stream) wait for it."""
-        ev = torch.cuda.Event()
-        ev.record()
-        _rt(self).setdefault("_writers", []).append(ev)
-
-    def _wait_writers(self, also_side_streams=False):
-        cur = torch.cuda.current_stream()
-        for ev in _rt(self).get("_writers", ()):
-            cur.wait_event(ev)
-        if also_side_streams:          # a non-atomic writer must not run next to ANY other backward kernel of the field
-            pool = _rt(self).get("_side_pool")
-            if pool is not None:
-                for st in pool["r"] + [pool["p"]]:
-                    if st != cur:
-                        cur.wait_stream(st)
-
-    def _queue_join(self):
-        """Once per backward pass: when the engine has run every node, the stream of the thread that called backward() waits for the
-        field's side streams - the optimiser step that follows then sees complete gradients (the engine itself only orders the
-        gradients it is handed, and in-place accumulation hands it none)."""
-        if _rt(self).get("_join_pending"):
-            return
-        _rt(self)["_join_pending"] = True
-        ref = weakref.ref(self)
-
-        def join():
-            f = ref()
-            if f is None:
-                return
-            _rt(f)["_join_pending"] = False
-            _rt(f)["_writers"] = []
-            pool = _rt(f).get("_side_pool")
-            if pool is not None:
-                cur = torch.cuda.current_stream()
-                for st in pool["r"] + [pool["p"]]:
-                    cur.wait_stream(st)
-
-        from torch.autograd import Variable
-        Variable._execution_engine.queue_callback(join)
+        """nvfi_grads over the 24 gradient tensors of both velocity nets, in _pde_params() order"""
+        return fs.fill(_lib.Grads(), grads, fs.PDE_MEMBERS)
 
     # ------------------------------------------------------------------ hot path
+    def _prep_rays(self, ray_o, ray_d, t):
+        """the rays of a call as contiguous fp32 (R, 3) device tensors and its time as an fp32 value (no CPU fallback exists)"""
+        if not ray_o.is_cuda or not self.aabb.is_cuda:
+            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
+        return ray_o.reshape(-1, 3).contiguous().float(), ray_d.reshape(-1, 3).contiguous().float(), float(np.float32(float(t)))
+
+    def _ray_buffers(self, R, dev, t, flags, maps=True):
+        """-> desc, workspace, (rgb, depth, acc, weights, counters) of a render of R rays at time t: the workspace as
+        nvfi_render_workspace_bytes_t plans it, the outputs un-initialised (maps=False: no rgb / depth / acc - the caller has its own)"""
+        desc = self._desc()
+        nbytes = _lib.bytes_of(_lib.lib().nvfi_render_workspace_bytes_t, C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rgb, depth, acc = (torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)) if maps else (None, None, None)
+        weights = torch.empty(R, desc.n_samples, device=dev)
+        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
+        return desc, ws, (rgb, depth, acc, weights, counters)
+
+    def _ray_call(self, ray_o, ray_d, t, flags):
+        """The set-up of a ray call: (ray_o, ray_d, t, flags) -> prepared rays and time, desc, workspace, the five standard outputs.  A caller
+        that draws its jitter between the two halves (forward, render_mse_backward_) calls them itself."""
+        ray_o, ray_d, t = self._prep_rays(ray_o, ray_d, t)
+        return (ray_o, ray_d, t) + self._ray_buffers(ray_o.shape[0], ray_o.device, t, flags)
+
     def forward(self, t, ray_o, ray_d, white_bg=True, ndc_ray=False, N_samples=-1, transfer_vel=False):
         """render one chunk of rays (tensorf_keyframe.py:613-755) -> rgb, depth, acc, weights, mask_map."""
         if ndc_ray:
             raise NotImplementedError("ndc rays are out of scope (ndc: False in every shipped config)")
         if N_samples > 0 and N_samples != self.nSamples:
             raise NotImplementedError("per-call N_samples override is not supported")
-        if not ray_o.is_cuda or not self.aabb.is_cuda:
-            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
-        ray_o = ray_o.reshape(-1, 3).contiguous().float()
-        ray_d = ray_d.reshape(-1, 3).contiguous().float()
+        t_dev = getattr(t, "dev", None)
+        ray_o, ray_d, t = self._prep_rays(ray_o, ray_d, t)
         R = ray_o.shape[0]
         training = self.training
         flags = 0
@@ -1113,8 +506,6 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             flags |= _lib.NVFI_TRANSFER
         if self.mask_field is not None:
             flags |= _lib.NVFI_WANT_MASK
-        t_dev = getattr(t, "dev", None)
-        t = float(np.float32(float(t)))
         if t_dev is not None:
             if self.mask_field is not None:
                 raise NotImplementedError("DeviceTime renders do not support the mask branch")
@@ -1166,30 +557,13 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             raise NotImplementedError("render_flow is an inference branch: call .eval() first")
         if not self.use_vel:
             raise NotImplementedError("render_flow needs a velocity field (use_vel=False)")
-        if not ray_o.is_cuda or not self.aabb.is_cuda:
-            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
+        from ..utils.flow_loss import flow_camera
         L = _lib.lib()
-        ray_o = ray_o.reshape(-1, 3).contiguous().float()
-        ray_d = ray_d.reshape(-1, 3).contiguous().float()
-        R, dev = ray_o.shape[0], ray_o.device
         flags = _lib.NVFI_WANT_FLOW | (_lib.NVFI_WHITE_BG if white_bg else 0) | (_lib.NVFI_TRANSFER if transfer_vel else 0)
-        t = float(np.float32(float(t)))
+        ray_o, ray_d, t, desc, ws, (rgb, depth, acc, weights, counters) = self._ray_call(ray_o, ray_d, t, flags)
+        R, dev = ray_o.shape[0], ray_o.device
         dt = float(np.float32(float(dt)))
-        pose, H, W, focal = None, 0, 0, 0.0
-        if camera is not None:
-            if isinstance(camera, (tuple, list)):
-                pose, H, W, focal = camera
-            else:
-                pose, H, W, focal = camera.pose, camera.height, camera.width, camera.focal
-            pose = torch.as_tensor(pose, dtype=torch.float32, device=dev)[:3, :4].contiguous()
-        desc = self._desc()
-        S = desc.n_samples
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        rgb, depth, acc = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
-        weights = torch.empty(R, S, device=dev)
-        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
+        pose, H, W, focal = (None, 0, 0, 0.0) if camera is None else flow_camera(camera, dev)
         vel_map, flow_map = torch.zeros(R, 3, device=dev), torch.zeros(R, 3, device=dev)
         flow2d = torch.zeros(R, 2, device=dev) if pose is not None else None
         if R > 0:
@@ -1197,7 +571,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                                          _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
                                          _lib.ptr(counters), _stream_ptr()))
             _lib.check(L.nvfi_render_flow(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_float(dt), C.c_int(flags),
-                                          _lib.ptr(weights), _lib.ptr(pose), C.c_int(int(H)), C.c_int(int(W)), C.c_float(float(focal)),
+                                          _lib.ptr(weights), _lib.ptr(pose), C.c_int(H), C.c_int(W), C.c_float(focal),
                                           _lib.ptr(vel_map), _lib.ptr(flow_map), _lib.ptr(flow2d), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
             self.last_counters = counters
         return rgb, depth, acc, weights, vel_map, flow_map, flow2d
@@ -1241,31 +615,16 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             raise NotImplementedError("render_objects is an inference branch: call .eval() first")
         if self.mask_field is None:
             raise NotImplementedError("render_objects needs a mask_field attached to the field")
-        if not ray_o.is_cuda or not self.aabb.is_cuda:
-            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
         L = _lib.lib()
-        ray_o = ray_o.reshape(-1, 3).contiguous().float()
-        ray_d = ray_d.reshape(-1, 3).contiguous().float()
-        R, dev = ray_o.shape[0], ray_o.device
         mf = self.mask_field
         K = mf.mask_dim
-        sel = self._select_vector(select, dev)
         flags = _lib.NVFI_WANT_MASK | (_lib.NVFI_WHITE_BG if white_bg else 0) | (_lib.NVFI_TRANSFER if transfer_vel else 0)
-        if sel is not None:
+        if select is not None:
             flags |= _lib.NVFI_WANT_SELECT
-        t = float(np.float32(float(t)))
-        md = _lib.MaskDesc()
-        md.n_layer, md.n_dim, md.mask_dim = len(mf.point_fc), mf.point_fc[0].out_features, K
-        for i, lin in enumerate(list(mf.point_fc) + [mf.mask_fc]):
-            md.W[i] = _lib.ptr(lin.weight); md.b[i] = _lib.ptr(lin.bias)
-        desc = self._desc()
-        S = desc.n_samples
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        rgb, depth, acc = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
-        weights = torch.empty(R, S, device=dev)
-        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
+        ray_o, ray_d, t, desc, ws, (rgb, depth, acc, weights, counters) = self._ray_call(ray_o, ray_d, t, flags)
+        R, dev = ray_o.shape[0], ray_o.device
+        sel = self._select_vector(select, dev)
+        md = _mask_desc(mf, mf._params())
         mask_map, obj_rgb = torch.zeros(R, K, device=dev), torch.zeros(R, K, 3, device=dev)
         obj_acc, obj_depth = torch.zeros(R, K, device=dev), torch.zeros(R, K, device=dev)
         if R > 0:
@@ -1310,11 +669,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         """mask branch of render_pts (tensorf_keyframe.py:673-676, 749-753); inference only."""
         L = _lib.lib()
         mf = self.mask_field
-        md = _lib.MaskDesc()
-        md.n_layer, md.n_dim, md.mask_dim = len(mf.point_fc), mf.point_fc[0].out_features, mf.mask_dim
-        lins = list(mf.point_fc) + [mf.mask_fc]
-        for i, lin in enumerate(lins):
-            md.W[i] = _lib.ptr(lin.weight); md.b[i] = _lib.ptr(lin.bias)
+        md = _mask_desc(mf, mf._params())
         out = torch.empty(R, mf.mask_dim, device=weights.device)
         desc = self._desc()
         ws = self._last_ws
@@ -1339,9 +694,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         xt = xt.reshape(-1, 4).contiguous().float()
         N = xt.shape[0]
         desc = self._desc()
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_vel_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=xt.device)
+        nb = _lib.bytes_of(L.nvfi_vel_workspace_bytes, C.byref(desc), C.c_int64(N))
+        ws = torch.empty(nb, dtype=torch.uint8, device=xt.device)
         u = torch.zeros(N, 6, device=xt.device)
         _lib.check(L.nvfi_vel_eval(C.byref(desc), C.c_int64(N), _lib.ptr(xt), _lib.ptr(u), C.c_int(int(gated)), _lib.ptr(ws),
                                    C.c_int64(ws.numel()), _stream_ptr()))
@@ -1359,9 +713,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         bb = base_times.reshape(-1).contiguous().float()
         N = x.shape[0]
         desc = self._desc()
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_vel_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device)
+        nb = _lib.bytes_of(L.nvfi_vel_workspace_bytes, C.byref(desc), C.c_int64(N))
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
         out = torch.empty_like(x)
         _lib.check(L.nvfi_integrate_pos(C.byref(desc), C.c_int64(N), _lib.ptr(x), _lib.ptr(tt), _lib.ptr(bb), _lib.ptr(out),
                                         _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
@@ -1378,7 +731,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             raise _lib.NvfiError("advect needs its points on the GPU (no CPU fallback exists)")
         if not self.use_vel:
             raise _lib.NvfiError("advect needs a field with a velocity net (use_vel)")
-        wparams = self._render_params()[19:31]
+        wparams = self._render_params()[fs.WEIGHT_NET]
         wants = torch.is_grad_enabled() and (pos.requires_grad or any(p.requires_grad for p in wparams))
 
         def scalar(v):
@@ -1394,11 +747,10 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                 raise NotImplementedError("advect: per-point times (a tensor t / t_target with more than one distinct value) have no gradient path")
             return self.integrate_pos(pos, t, t_target).reshape(pos.shape)
         desc = self._desc()
-        nb = C.c_int64(0)
         if wants and (desc.vel_fp16 & 3) in (1, 2):
             raise NotImplementedError("advect: the fp16-input modes (vel_fp16 1 / 2) have no adjoint")
         if (desc.vel_fp16 & 3) not in (1, 2):      # the step limit, decided on the host before anything is launched
-            _lib.check(_lib.lib().nvfi_advect_grad_workspace_bytes(C.byref(desc), C.c_int64(0), C.c_float(ts), C.c_float(t1s), C.byref(nb)))
+            _lib.bytes_of(_lib.lib().nvfi_advect_grad_workspace_bytes, C.byref(desc), C.c_int64(0), C.c_float(ts), C.c_float(t1s))
         x = pos.reshape(-1, 3).contiguous().float()
         if not wants:
             tt = torch.full((x.shape[0],), ts, dtype=torch.float32, device=x.device)
@@ -1425,7 +777,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         The plane gradients are float atomics (not bit-repeatable); the gradient at `xyzt` repeats bit for bit."""
         if not (isinstance(xyzt, torch.Tensor) and xyzt.is_cuda):
             raise _lib.NvfiError("lookup_density needs its points on the GPU (no CPU fallback exists)")
-        planes = self._render_params()[:6]
+        planes = self._render_params()[fs.DENSITY]
         if not (torch.is_grad_enabled() and (xyzt.requires_grad or any(p.requires_grad for p in planes))):
             return self.compute_densityfeature(xyzt)
         return _DensityLookupFn.apply(self, xyzt.reshape(-1, 4).contiguous().float(), *planes)
@@ -1435,7 +787,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         six appearance planes and basis_mat.weight.  renderModule on these features stays forward-only."""
         if not (isinstance(xyzt, torch.Tensor) and xyzt.is_cuda):
             raise _lib.NvfiError("lookup_appfeature needs its points on the GPU (no CPU fallback exists)")
-        params = self._render_params()[6:13]
+        params = self._render_params()[fs.APP]
         if not (torch.is_grad_enabled() and (xyzt.requires_grad or any(p.requires_grad for p in params))):
             return self.compute_appfeature(xyzt)
         return _AppLookupFn.apply(self, xyzt.reshape(-1, 4).contiguous().float(), *params)
@@ -1471,9 +823,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         N = q.shape[0]
         rgb = torch.empty(N, 3, device=q.device)
         desc = self._desc()
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_app_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=q.device)
+        nb = _lib.bytes_of(L.nvfi_app_workspace_bytes, C.byref(desc), C.c_int64(N))
+        ws = torch.empty(nb, dtype=torch.uint8, device=q.device)
         _lib.check(L.nvfi_app_at(C.byref(desc), C.c_int64(N), _lib.ptr(q), _lib.ptr(v), _lib.ptr(rgb), _lib.ptr(ws),
                                  C.c_int64(ws.numel()), _stream_ptr()))
         return rgb
@@ -1488,9 +839,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         N = x.shape[0]
         rgb = torch.empty(N, 3, device=x.device)
         desc = self._desc()
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_app_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
-        ws = torch.empty(2 * nb.value, dtype=torch.uint8, device=x.device)
+        nb = _lib.bytes_of(L.nvfi_app_workspace_bytes, C.byref(desc), C.c_int64(N))
+        ws = torch.empty(2 * nb, dtype=torch.uint8, device=x.device)
         _lib.check(L.nvfi_render_mlp(C.byref(desc), C.c_int64(N), _lib.ptr(x), _lib.ptr(v), _lib.ptr(fe), _lib.ptr(rgb), _lib.ptr(ws),
                                      C.c_int64(ws.numel()), _stream_ptr()))
         return rgb
@@ -1521,18 +871,13 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         t = t.reshape(-1).contiguous().float()
         P = points.shape[0]
         desc = self._desc()
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_pde_workspace_bytes(C.byref(desc), C.c_int64(P), C.byref(nbytes)))
-        ws = self._scratch("pde", nbytes.value, points.device)
+        nbytes = _lib.bytes_of(L.nvfi_pde_workspace_bytes, C.byref(desc), C.c_int64(P))
+        ws = self._scratch("pde", nbytes, points.device)
         out = torch.empty(4, device=points.device)       # written by k_pde_finish
-        grads = []
         if grad_targets is not None:
             grads = list(grad_targets)
         else:
-            for p in self._pde_params():
-                if p.grad is None:
-                    p.grad = torch.zeros_like(p)
-                grads.append(p.grad)
+            grads, _ = self._grad_targets(self._pde_params(), [True] * fs.N_PDE, mode=True)
         G = self._grads_struct_vel(grads)
         counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=points.device)
         # no host_info: the call does not wait for the device; the kept count is out[1] / counters[4] (device side)
@@ -1569,15 +914,14 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         L = _lib.lib()
         pts = points.detach().reshape(-1, 3).contiguous().float()
         N = pts.shape[0]
-        desc = self._desc() if params is None else self._desc(list(params) + self._render_params()[13:])
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_char_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
-        ws = self._scratch("char", nb.value, pts.device)
+        desc = self._desc() if params is None else self._desc(self._params_with(fs.PLANES, params))
+        nb = _lib.bytes_of(L.nvfi_char_workspace_bytes, C.byref(desc), C.c_int64(N))
+        ws = self._scratch("char", nb, pts.device)
         terms = torch.empty(2, device=pts.device)
         points0 = torch.empty_like(pts)
         G = None
         if grads is not None:
-            for g, p in zip(grads, self._render_params()[:13]):
+            for g, p in zip(grads, self._render_params()[fs.PLANES]):
                 if g is not None and g.stride() != p.stride():
                     raise _lib.NvfiError("a gradient target must share the memory layout of its parameter (channels_last planes)")
             G = C.byref(self._grads_struct(list(grads)))
@@ -1591,7 +935,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         tensor with autograd history onto the twelve planes and basis_mat; the two terms of the last call are kept in `last_char_terms`."""
         if not self.use_vel:
             raise _lib.NvfiError("characteristic_loss needs the velocity field (use_vel=False): there is nothing to advect the points with")
-        loss, terms, points0 = _CharFn.apply(self, points, float(t), *self._render_params()[:13])
+        loss, terms, points0 = _CharFn.apply(self, points, float(t), *self._render_params()[fs.PLANES])
         self.last_char_terms = terms
         return (loss, points0) if return_points0 else loss
 
@@ -1614,14 +958,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             points = points_or_n
         else:
             points = torch.rand(int(points_or_n), 3, device=self.aabb.device) * 2 - 1
-        grads = []
-        for p in self._render_params()[:13]:
-            if not p.requires_grad:
-                grads.append(None)
-                continue
-            if p.grad is None:
-                p.grad = torch.zeros_like(p)
-            grads.append(p.grad)
+        params = self._render_params()[fs.PLANES]
+        grads, _ = self._grad_targets(params, [p.requires_grad for p in params], mode=True)
         terms, _ = self._char_call(points, t, weight, grads)
         self.last_char_terms = terms
         return terms[0] + terms[1]
@@ -1678,22 +1016,20 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         a loop or a captured graph.  The UN-scaled, un-weighted value (0-dim device tensor) is appended behind the distortion value.  The mask
         branch and DeviceTime renders raise NotImplementedError."""
         L = _lib.lib()
-        if not ray_o.is_cuda or not self.aabb.is_cuda:
-            raise _lib.NvfiError("NVFi HIP kernels need the field and the rays on the GPU (no CPU fallback exists)")
+        t_dev = getattr(t, "dev", None)
+        ray_o, ray_d, t = self._prep_rays(ray_o, ray_d, t)
         if self.mask_field is not None:
             raise NotImplementedError("render_mse_backward_ does not drive the mask branch")
         distortion_weight = float(distortion_weight)
         if not distortion_weight >= 0.0:
             raise ValueError(f"distortion_weight must not be negative ({distortion_weight})")
         if target_flow is not None:
-            if getattr(t, "dev", None) is not None:
+            if t_dev is not None:
                 raise NotImplementedError("render_mse_backward_: the flow term does not support DeviceTime renders")
             if flow_dt is None or flow_camera is None:
                 raise ValueError("target_flow needs flow_dt and flow_camera")
             if not self.use_vel:
                 raise _lib.NvfiError("the flow term needs a field with a velocity net (use_vel)")
-        ray_o = ray_o.reshape(-1, 3).contiguous().float()
-        ray_d = ray_d.reshape(-1, 3).contiguous().float()
         target = target.reshape(-1, 3).contiguous().float()
         R = ray_o.shape[0]
         dev = ray_o.device
@@ -1702,15 +1038,10 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             jitter = self._jitter(R, dev)          # the reference's CPU-generator draw (tensorf_base.py:302-306)
         if white_bg or bool(torch.rand((1,)) < 0.5):    # tensorf_keyframe.py:740
             flags |= _lib.NVFI_WHITE_BG
-        t_dev = getattr(t, "dev", None)
-        t = float(np.float32(float(t)))
         ps = self._render_params()
-        desc = self._desc()
+        desc, ws, (_, _, _, weights, counters) = self._ray_buffers(R, dev, t, flags, maps=False)
         S = desc.n_samples
-        nbytes = C.c_int64(0)
-        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t), C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        a3, a1 = (3 * R + 63) // 64 * 64, (R + 63) // 64 * 64          # rgb | g_rgb | depth | acc | loss [| g_depth] [| distortion workspace]: one allocation, 256-byte aligned pieces
+        a3, a1 = round64(3 * R), round64(R)          # rgb | g_rgb | depth | acc | loss [| g_depth] [| distortion workspace]: one allocation, 256-byte aligned pieces
         o_gd = 2 * a3 + 2 * a1 + 64
         o_dw = o_gd + (a1 if target_depth is not None else 0)          # R doubles for nvfi_ray_distortion's mean: 2 * a1 floats
         out = torch.empty(o_dw + (2 * a1 if distortion_weight > 0.0 else 0), device=dev)
@@ -1731,8 +1062,6 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             elif target_depth.numel() != R:
                 raise ValueError(f"target_depth must hold one depth per ray ({R}) unless depth_index selects from an image")
             g_depth = out[o_gd:o_gd + R]
-        weights = torch.empty(R, S, device=dev)
-        counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
         st = _stream_ptr()
         _lib.check(L.nvfi_render_fwd_mse(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(jitter), C.c_float(t), _lib.ptr(t_dev),
                                          C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
@@ -1744,11 +1073,10 @@ class TensorVMKeyframeTimeKplane(nn.Module):
                                          _lib.ptr(loss[_LOSS_DEPTH:]), _lib.ptr(g_depth), _lib.ptr(loss[_LOSS_DEPTH_COUNT:]), st))
         g_w = None
         if distortion_weight > 0.0:
-            dbytes = C.c_int64(0)
-            _lib.check(L.nvfi_ray_distortion_workspace_bytes(C.c_int64(R), C.byref(dbytes)))
+            dbytes = _lib.bytes_of(L.nvfi_ray_distortion_workspace_bytes, C.c_int64(R))
             dws = out[o_dw:]
-            if dbytes.value > dws.numel() * 4:
-                raise _lib.NvfiError(f"nvfi_ray_distortion wants a workspace of {dbytes.value} bytes, {dws.numel() * 4} were set aside")
+            if dbytes > dws.numel() * 4:
+                raise _lib.NvfiError(f"nvfi_ray_distortion wants a workspace of {dbytes} bytes, {dws.numel() * 4} were set aside")
             g_w = torch.empty(R, S, device=dev)
             _lib.check(L.nvfi_ray_distortion(C.c_int64(R), C.c_int(S), _lib.ptr(weights), C.c_float(self.distortion_delta()),
                                              C.c_float(float(loss_scale) * distortion_weight), None, _lib.ptr(loss[_LOSS_DISTORTION:]), None, _lib.ptr(g_w),
@@ -1802,7 +1130,7 @@ class TensorVMKeyframeTimeKplane(nn.Module):
             raise ValueError("flow_loss: the workspace of that render was released by its backward; call flow_loss before backward")
         if node.t_on_device:
             raise NotImplementedError("flow_loss: DeviceTime renders are not supported (the flow loss plans with a host-scalar time)")
-        wparams = self._render_params()[19:31]
+        wparams = self._render_params()[fs.WEIGHT_NET]
         w_in = weights if weight_grad else weights.detach()
         if not torch.is_grad_enabled():
             w_in = weights.detach()
@@ -1889,16 +1217,12 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         followed by backward: one pass per plane that ACCUMULATES the weighted gradients into p.grad and returns the
         three un-weighted loss values (device tensor [L1, TVd, TVa]).  Call it next to loss.backward()."""
         L = _lib.lib()
-        ps = self._render_params()
-        grads = []
-        for p in ps[:9]:
-            if p.grad is None:
-                p.grad = torch.zeros_like(p)
-            grads.append(p.grad)
-        for g, p in zip(grads, ps[:9]):
+        ps = self._render_params()[fs.REG]
+        grads, _ = self._grad_targets(ps, [True] * len(ps), mode=True)
+        for g, p in zip(grads, ps):
             if g.stride() != p.stride():
                 raise _lib.NvfiError("plane .grad must share the channels_last layout of its parameter")
-        G = self._grads_struct(grads + [None] * 22)
+        G = self._grads_struct(fs.at(fs.REG, grads))
         out = torch.empty(3, device=ps[0].device)
         desc = self._desc()
         if isinstance(w_l1, torch.Tensor):       # the three weights as one fp32[3] CUDA tensor (hipGraph replay: they decay every iteration)
@@ -1961,9 +1285,8 @@ class TensorVMKeyframeTimeKplane(nn.Module):
         N = flat.shape[0]
         alpha = torch.zeros(N, device=dev)
         desc = self._desc()
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_alpha_workspace_bytes(C.byref(desc), C.c_int64(N), C.byref(nb)))
-        ws = self._scratch("alpha", nb.value, dev)
+        nb = _lib.bytes_of(L.nvfi_alpha_workspace_bytes, C.byref(desc), C.c_int64(N))
+        ws = self._scratch("alpha", nb, dev)
         for t in (np.linspace(0, 59, 60) / 60):
             _lib.check(L.nvfi_compute_alpha(C.byref(desc), C.c_int64(N), _lib.ptr(flat), C.c_float(float(np.float32(t))), C.c_int(int(transfer)),
                                             C.c_float(self._step_host), C.c_int(1), _lib.ptr(alpha), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))

@@ -9,10 +9,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .._lib import stream_ptr as _stream_ptr
 
 
 def _points(xyzt):

@@ -12,12 +12,9 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._lib import stream_ptr as _stream_ptr
 
 KINDS = {"l2": 0, "huber": 1}
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def flow_camera(camera, device):
@@ -39,22 +36,11 @@ def flow_loss_plan(desc, R, t, dt, max_workspace_bytes=1 << 30):
     ~10.8 KB per entry and RK2 step).  Raises NvfiError (error 2) for what the library refuses: use_vel == 0, vel_fp16 1 / 2, more than 64 steps."""
     L = _lib.lib()
     cap = int(R) * int(desc.n_samples)
-    nb = C.c_int64(0)
 
     def nbytes(n):
-        _lib.check(L.nvfi_flow_loss_workspace_bytes(C.byref(desc), C.c_int64(R), C.c_float(t), C.c_float(dt), C.c_int64(n), C.byref(nb)))
-        return nb.value
+        return _lib.bytes_of(L.nvfi_flow_loss_workspace_bytes, C.byref(desc), C.c_int64(R), C.c_float(t), C.c_float(dt), C.c_int64(n))
 
-    chunk = cap
-    if nbytes(cap) > max_workspace_bytes:
-        b1, b2 = nbytes(128), nbytes(256)
-        if b1 > max_workspace_bytes:
-            raise _lib.NvfiError(f"flow loss: max_workspace_bytes={max_workspace_bytes} is below the {b1} bytes one 128-entry group needs")
-        chunk = 128 * (1 + (max_workspace_bytes - b1) // max(b2 - b1, 1))
-        while chunk > 128 and nbytes(chunk) > max_workspace_bytes:
-            chunk -= 128
-        chunk = min(chunk, cap)
-    return chunk, nbytes(chunk), (cap + chunk - 1) // chunk
+    return _lib.plan_chunks(nbytes, cap, max_workspace_bytes, "flow loss")
 
 
 def flow_loss_raw(desc, render_ws, flags, rays_o, rays_d, weights, t, dt, camera, target, valid=None, kind="l2", huber_delta=1.0,

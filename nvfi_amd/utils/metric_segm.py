@@ -23,12 +23,9 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._lib import stream_ptr as _stream_ptr
 
 MAX_LABELS = 32
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---------------------------------------------------------------- stage 1: frames -> confusion (GPU)

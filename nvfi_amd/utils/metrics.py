@@ -16,6 +16,7 @@ import os
 import torch
 
 from .. import _lib
+from .._lib import stream_ptr as _stream_ptr
 
 
 def mse2psnr(mse):
@@ -34,10 +35,6 @@ class PSNR(object):
     def __call__(self, pred, gt):
         mse = torch.mean((pred - gt) ** 2)
         return 10 * torch.log10(1 / mse)
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def ssim_stats(pred, gt, layout="BCHW", L=None, per_image_range=False):

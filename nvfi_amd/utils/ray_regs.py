@@ -15,10 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .._lib import stream_ptr as _stream_ptr
 
 
 def distortion_workspace(R, device):

@@ -233,6 +233,42 @@ def test_fused_form_weight_and_frozen_tensor(kind):
         c.model.zero_grad(set_to_none=True)
 
 
+def test_arena_mode_scales_into_the_arena_and_accumulates():
+    """accumulate_grads_inplace = "arena": with all 13 tensors trainable the backward adds g x (unit-weight gradients) to the head of the
+    field's flat gradient buffer in one launch and hands autograd nothing; a second backward accumulates; with one tensor frozen the node
+    scales and returns its own gradients instead, and the frozen tensor keeps .grad = None"""
+    from nvfi_amd.models.tensorf_keyframe import _rt
+    c = ctx_of("A")
+    f, pts = c.field, c.points[:63].contiguous()
+    t = c.tmax
+    frozen = f.app_plane_space[1]
+    fname = "app_plane_space.1"
+    mode = f.accumulate_grads_inplace
+    try:
+        f.accumulate_grads_inplace = "arena"
+        c.model.zero_grad(set_to_none=True)
+        for k in (1, 2):
+            loss, points0 = f.characteristic_loss_at(pts, t, return_points0=True)
+            y, _, _ = yardstick(c, pts, points0, t)
+            (0.3 * loss).backward()
+            views = _rt(f)["_arena"]["views"]
+            assert all(p.grad is views[id(p)] for p in f._render_params()[:13]), "the gradients are not the arena's views"
+            compare(c, f"A arena, backward {k}", f.last_char_terms.cpu().numpy(), grads_of(c.model), y, scale=0.3 * k)
+        c.model.zero_grad(set_to_none=True)
+        frozen.requires_grad_(False)
+        loss, points0 = f.characteristic_loss_at(pts, t, return_points0=True)
+        y, _, _ = yardstick(c, pts, points0, t)
+        (0.3 * loss).backward()
+        assert frozen.grad is None
+        g3 = grads_of(c.model)
+        g3[fname] = 0.3 * y["grads"][fname]
+        compare(c, "A arena, one tensor frozen", f.last_char_terms.cpu().numpy(), g3, y, scale=0.3)
+    finally:
+        f.accumulate_grads_inplace = mode
+        frozen.requires_grad_(True)
+        c.model.zero_grad(set_to_none=True)
+
+
 def untouched_clamp_texels(c, points0, y):
     """per plane parameter name: bool (H, W) - texels a border-clamping rule would touch for out-of-plane taps of the 0 side and that the
     loss, under zero padding, does not depend on (yardstick gradient exactly zero in every channel)"""
