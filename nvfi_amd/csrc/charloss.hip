@@ -4,14 +4,12 @@
 // Value and gradients (twelve planes + basis_mat) come out of ONE pass per plane family: no gradient depends on the loss total, so every
 // contribution is scaled by a weight known before the launch.  The time is uniform per call and sits ON a keyframe, so the time coordinate of
 // both lookups is an integer row (a host scalar): the time planes are read with the two x-taps of that row, the space planes with four taps.
-// Lane layout as in scatter_atomic.hip - lanes are CHANNELS, a tap is one contiguous texel vector:
-//   density (24 channels)  lane = 2 * channel + x-tap: one load / atomic instruction covers two neighbouring texels (192 B)
-//   appearance (48)        lane = channel: one texel per instruction (192 B)
-// basis_mat has no bias: a_t - a_0 = W (g_t - g_0).  W (app_dim x 48) sits in LDS; per point one lane per output row forms y = W dg, one lane
-// per channel forms W^T y, and dW = sum y dg^T is kept in registers per wave (lane = column), reduced per workgroup in LDS, and only then added
-// to global memory.  Plane gradients are float atomics (the call is not covered by NVFI_DETERMINISTIC).
+// One wave per point, lanes are channels (pointwave.h: the lane layouts, the tap sets, basis_mat in LDS, the dW flush); the loss sums follow reduce.h.
+// basis_mat has no bias: a_t - a_0 = W (g_t - g_0).  Per point one lane per output row forms y = W dg, one lane per channel forms W^T y, and
+// dW = sum y dg^T.  Plane gradients are float atomics (the call is not covered by NVFI_DETERMINISTIC).
 #include <string.h>
-#include "common.h"
+#include "reduce.h"
+#include "pointwave.h"
 
 struct CharArgs {
     nvfi_field_desc f;
@@ -24,20 +22,8 @@ struct CharArgs {
     double* acc;           // [2] sum (d_t - d_0)^2, sum |W dg|^2
 };
 
-__device__ __forceinline__ float uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ float lane_bcast(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
-__device__ __forceinline__ double lane_bcast_d(double v, int l) {
-    const long long q = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)q, l), hi = __builtin_amdgcn_readlane((int)(q >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
+// The tap sets of a point are formed HERE, not by common.h's plane_setups as in lookup.hip: the time coordinate is the integer keyframe row, and
+// DESIGN 4.15 measured 4.27 x the allowed error with the fp32 setup.
 // One axis of a tap set.  The texel coordinate is formed in double and only the two weights are rounded to fp32: an fp32 coordinate
 // carries half an ulp of a number up to W into the weights (5e-7 absolute at W = 16), which is as large as the whole error the loss may
 // show at a single point.  The points themselves are fp32 data.  The setup is wave-uniform, so the doubles cost a few scalar-like ops per point.
@@ -75,166 +61,120 @@ __device__ __forceinline__ void char_setups(const nvfi_field_desc& f, const floa
     bl_row(x, f.G[0], row, b[5]);
 }
 
-// ---- density layout: lane = 2 * channel + x-tap; both lanes of a pair end up with the channel's bilinear value
-__device__ __forceinline__ void pair_vals(const float* const* pl, const Bl* b, int ch, int dx0, bool lane_on, float* val) {
+// ---- density layout: both lanes of a pair end up with the channel's bilinear value.  Loads under the mask (ch is not clamped in lanes >= 48)
+__device__ __forceinline__ void pair_vals(const float* const* pl, const Bl* b, int ch, int dx0, bool lane_on, LaneTaps<2>* t, float* val) {
 #pragma unroll
     for (int p = 0; p < 6; ++p) {
-        const bool my0 = lane_on && (dx0 ? b[p].m1 : b[p].m0), my1 = lane_on && (dx0 ? b[p].m3 : b[p].m2);
-        const float wx = dx0 ? b[p].w : b[p].e;
-        const size_t o0 = (size_t)(b[p].base + dx0) * 24 + ch, o1 = o0 + (size_t)b[p].W * 24;
-        const float v0 = my0 ? pl[p][o0] : 0.f, v1 = my1 ? pl[p][o1] : 0.f;
-        const float part = (my0 ? v0 * (wx * b[p].s) : 0.f) + (my1 ? v1 * (wx * b[p].n) : 0.f);
+        float wx;
+        density_taps(b[p], ch, dx0, lane_on, t[p], wx);
+        const float v0 = t[p].m[0] ? pl[p][t[p].o[0]] : 0.f, v1 = t[p].m[1] ? pl[p][t[p].o[1]] : 0.f;
+        const float part = (t[p].m[0] ? v0 * t[p].w[0] : 0.f) + (t[p].m[1] ? v1 * t[p].w[1] : 0.f);
         val[p] = part + __shfl_xor(part, 1);
     }
 }
-__device__ __forceinline__ void pair_scatter(float* const* gp, const Bl* b, int ch, int dx0, bool lane_on, const float* val, float g) {
-    float L[6], R[6];
-    L[0] = g;
+// g x the product of the other five values into the lane's texels of every plane that has a gradient buffer
+template <int NT> __device__ __forceinline__ void char_scatter(float* const* gp, const LaneTaps<NT>* t, const float* val, float g) {
+    float o[6];
+    other_five(val, g, o);
 #pragma unroll
-    for (int p = 1; p < 6; ++p) L[p] = L[p - 1] * val[p - 1];
-    R[5] = 1.f;
-#pragma unroll
-    for (int p = 4; p >= 0; --p) R[p] = R[p + 1] * val[p + 1];
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-        if (!gp[p] || !lane_on) continue;
-        const float o = L[p] * R[p];
-        const bool my0 = dx0 ? b[p].m1 : b[p].m0, my1 = dx0 ? b[p].m3 : b[p].m2;
-        const float wx = dx0 ? b[p].w : b[p].e;
-        const size_t o0 = (size_t)(b[p].base + dx0) * 24 + ch, o1 = o0 + (size_t)b[p].W * 24;
-        if (my0) atomicAdd(gp[p] + o0, (wx * b[p].s) * o);
-        if (my1) atomicAdd(gp[p] + o1, (wx * b[p].n) * o);
-    }
+    for (int p = 0; p < 6; ++p)
+        if (gp[p]) scatter_taps(gp[p], t[p], o[p]);
 }
-__device__ __forceinline__ float prod6(const float* v) { return ((v[0] * v[1]) * v[2]) * ((v[3] * v[4]) * v[5]); }
 
 __global__ __launch_bounds__(256) void k_char_density(CharArgs a) {
     const nvfi_field_desc& f = a.f;
-    const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-    const int64_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * nwv + (threadIdx.x >> 6)), wtot = (int64_t)gridDim.x * nwv;
-    const int ch = lane >> 1, dx0 = lane & 1;
+    const PointWalk w;
+    const int lane = w.lane, ch = lane >> 1, dx0 = lane & 1;
     const bool lane_on = lane < 48;
     const float* pl[6]; float* gp[6];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { pl[p] = f.dps[p]; pl[3 + p] = f.dpt[p]; gp[p] = a.g.dps[p]; gp[3 + p] = a.g.dpt[p]; }
+    family_planes(f.dps, f.dpt, pl);
+    family_planes(a.g.dps, a.g.dpt, gp);
     double lsum = 0.0;
 #pragma unroll 1
-    for (int64_t n = wave0; n < a.N; n += wtot) {
+    for (int64_t n = w.wave0; n < a.N; n += w.wtot) {
         Bl bt[6], b0[6];
         char_setups(f, a.x + 3 * n, a.row, bt);
         char_setups(f, a.x0 + 3 * n, 0, b0);
+        LaneTaps<2> tt[6], t0[6];
         float vt[6], v0[6];
-        pair_vals(pl, bt, ch, dx0, lane_on, vt);
-        pair_vals(pl, b0, ch, dx0, lane_on, v0);
+        pair_vals(pl, bt, ch, dx0, lane_on, tt, vt);
+        pair_vals(pl, b0, ch, dx0, lane_on, t0, v0);
         const float diff = wave_sum((lane_on && !dx0) ? prod6(vt) - prod6(v0) : 0.f);      // d_t - d_0, the same in every lane
         lsum += (double)diff * (double)diff;
         const float g = a.s_d * diff;
-        pair_scatter(gp, bt, ch, dx0, lane_on, vt, g);
-        pair_scatter(gp, b0, ch, dx0, lane_on, v0, -g);
+        char_scatter(gp, tt, vt, g);
+        char_scatter(gp, t0, v0, -g);
     }
     if (lane == 0 && lsum != 0.0) atomicAdd(a.acc, lsum);
 }
 
-// ---- appearance layout: lane = channel (48 of 64 lanes)
+// ---- appearance layout
 // returns the channel's product of the six bilinear values in double (the value path: g_t - g_0 cancels, and an fp32 product would hand the
-// cancellation 3e-7 of each side); val[] keeps the six values in fp32 for the gradient's other-five products
-__device__ __forceinline__ double full_vals(const float* const* pl, const Bl* b, int ch, bool lane_on, float* val) {
+// cancellation 3e-7 of each side) - its own weights in double, not the taps' fp32 ones; val[] keeps the six values in fp32 for the gradient's
+// other-five products.  Loads under the mask
+__device__ __forceinline__ double full_vals(const float* const* pl, const Bl* b, int ch, bool lane_on, LaneTaps<4>* t, float* val) {
     double prod = 1.0;
 #pragma unroll
     for (int p = 0; p < 6; ++p) {
-        const size_t o0 = (size_t)b[p].base * 48 + ch, o1 = o0 + (size_t)b[p].W * 48;
-        const bool m0 = lane_on && b[p].m0, m1 = lane_on && b[p].m1, m2 = lane_on && b[p].m2, m3 = lane_on && b[p].m3;
-        const float v0 = m0 ? pl[p][o0] : 0.f, v1 = m1 ? pl[p][o0 + 48] : 0.f, v2 = m2 ? pl[p][o1] : 0.f, v3 = m3 ? pl[p][o1 + 48] : 0.f;
+        app_taps(b[p], ch, lane_on, t[p]);
+        const bool* m = t[p].m;
+        const float v0 = m[0] ? pl[p][t[p].o[0]] : 0.f, v1 = m[1] ? pl[p][t[p].o[1]] : 0.f, v2 = m[2] ? pl[p][t[p].o[2]] : 0.f, v3 = m[3] ? pl[p][t[p].o[3]] : 0.f;
         const double e = b[p].e, w = b[p].w, n = b[p].n, s = b[p].s;
-        const double v = (m0 ? (double)v0 * (e * s) : 0.0) + (m1 ? (double)v1 * (w * s) : 0.0) + (m2 ? (double)v2 * (e * n) : 0.0) +
-                         (m3 ? (double)v3 * (w * n) : 0.0);
+        const double v = (m[0] ? (double)v0 * (e * s) : 0.0) + (m[1] ? (double)v1 * (w * s) : 0.0) + (m[2] ? (double)v2 * (e * n) : 0.0) +
+                         (m[3] ? (double)v3 * (w * n) : 0.0);
         val[p] = (float)v;
         prod *= v;
     }
     return lane_on ? prod : 0.0;
 }
-__device__ __forceinline__ void full_scatter(float* const* gp, const Bl* b, int ch, bool lane_on, const float* val, float g) {
-    float L[6], R[6];
-    L[0] = g;
-#pragma unroll
-    for (int p = 1; p < 6; ++p) L[p] = L[p - 1] * val[p - 1];
-    R[5] = 1.f;
-#pragma unroll
-    for (int p = 4; p >= 0; --p) R[p] = R[p + 1] * val[p + 1];
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-        if (!gp[p] || !lane_on) continue;
-        const float o = L[p] * R[p];
-        const size_t o0 = (size_t)b[p].base * 48 + ch, o1 = o0 + (size_t)b[p].W * 48;
-        if (b[p].m0) atomicAdd(gp[p] + o0, (b[p].e * b[p].s) * o);
-        if (b[p].m1) atomicAdd(gp[p] + o0 + 48, (b[p].w * b[p].s) * o);
-        if (b[p].m2) atomicAdd(gp[p] + o1, (b[p].e * b[p].n) * o);
-        if (b[p].m3) atomicAdd(gp[p] + o1 + 48, (b[p].w * b[p].n) * o);
-    }
-}
 
-#define CH_WSTRIDE 49      // LDS row stride of basis_mat: odd, so lanes that read a column (row = lane) hit 32 different banks
 __global__ __launch_bounds__(256) void k_char_app(CharArgs a) {
-    __shared__ float Wl[32 * CH_WSTRIDE];      // basis_mat, rows >= app_dim zero
+    __shared__ float Wl[32 * PW_WSTRIDE];      // basis_mat
     __shared__ float red[32 * 48];             // dW of the workgroup
     const nvfi_field_desc& f = a.f;
-    const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-    const int64_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * nwv + (threadIdx.x >> 6)), wtot = (int64_t)gridDim.x * nwv;
+    const PointWalk w;
+    const int lane = w.lane;
     const bool lane_on = lane < 48;
     const int ch = lane_on ? lane : 0, jrow = lane & 31;
-    const int app_dim = f.app_dim;
-    for (int k = threadIdx.x; k < 32 * 48; k += blockDim.x) {
-        const int j = k / 48, c = k - 48 * j;
-        Wl[j * CH_WSTRIDE + c] = j < app_dim ? f.basis[k] : 0.f;
-        red[k] = 0.f;
-    }
-    __syncthreads();
+    stage_basis(f, Wl, red);
     const float* pl[6]; float* gp[6];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { pl[p] = f.aps[p]; pl[3 + p] = f.apt[p]; gp[p] = a.g.aps[p]; gp[3 + p] = a.g.apt[p]; }
+    family_planes(f.aps, f.apt, pl);
+    family_planes(a.g.aps, a.g.apt, gp);
     const bool want_w = a.g.basis != nullptr;
     float accW[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) accW[j] = 0.f;
     double lsum = 0.0;
 #pragma unroll 1
-    for (int64_t n = wave0; n < a.N; n += wtot) {
+    for (int64_t n = w.wave0; n < a.N; n += w.wtot) {
         Bl bt[6], b0[6];
         char_setups(f, a.x + 3 * n, a.row, bt);
         char_setups(f, a.x0 + 3 * n, 0, b0);
+        LaneTaps<4> tt[6], t0[6];
         float vt[6], v0[6];
-        const double gt = full_vals(pl, bt, ch, lane_on, vt);
-        const double g0 = full_vals(pl, b0, ch, lane_on, v0);
+        const double gt = full_vals(pl, bt, ch, lane_on, tt, vt);
+        const double g0 = full_vals(pl, b0, ch, lane_on, t0, v0);
         const double dgd = gt - g0;                                        // g_t - g_0 of this lane's channel (0 in lanes >= 48)
         const float dg = (float)dgd;
         double yd = 0.0;                                                   // lane j < 32: (W dg)_j, in double: the value path
 #pragma unroll 8
-        for (int c = 0; c < 48; ++c) yd += (double)Wl[jrow * CH_WSTRIDE + c] * lane_bcast_d(dgd, c);
+        for (int c = 0; c < 48; ++c) yd += (double)Wl[jrow * PW_WSTRIDE + c] * lane_bcast(dgd, c);
         if (lane >= 32) yd = 0.0;
-        lsum += wave_sum_d(yd * yd);
+        lsum += wave_sum(yd * yd);
         const float y = (float)yd;
         float gl = 0.f;                                                    // lane c < 48: (W^T y)_c
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
             const float yj = lane_bcast(y, j);
-            gl += Wl[j * CH_WSTRIDE + ch] * yj;
+            gl += Wl[j * PW_WSTRIDE + ch] * yj;
             if (want_w) accW[j] += yj * dg;
         }
         gl *= a.s_a;
-        full_scatter(gp, bt, ch, lane_on, vt, gl);
-        full_scatter(gp, b0, ch, lane_on, v0, -gl);
+        char_scatter(gp, tt, vt, gl);
+        char_scatter(gp, t0, v0, -gl);
     }
     if (lane == 0 && lsum != 0.0) atomicAdd(a.acc + 1, lsum);
-    if (want_w) {
-        if (lane_on) {
-#pragma unroll
-            for (int j = 0; j < 32; ++j)
-                if (accW[j] != 0.f) atomicAdd(&red[j * 48 + ch], accW[j]);
-        }
-        __syncthreads();
-        for (int k = threadIdx.x; k < app_dim * 48; k += blockDim.x)
-            if (red[k] != 0.f) atomicAdd(a.g.basis + k, a.s_a * red[k]);
-    }
+    if (want_w) flush_dw(accW, red, ch, lane_on, f.app_dim, a.s_a, a.g.basis);
 }
 
 __global__ void k_char_times(int64_t N, float t, float* tt, float* tb) {
@@ -313,9 +253,7 @@ extern "C" int nvfi_char_loss(const nvfi_field_desc* f, int64_t N, const float* 
     }
     a.s_d = (float)((double)weight * 2.0 / (double)N);
     a.s_a = (float)((double)weight * 2.0 / ((double)N * (double)f->app_dim));
-    // a wave walks the points with a grid stride; at most two workgroups per CU, so that the per-workgroup flush of dW stays a small share
-    const int64_t want = (N + 15) / 16, cap = 2 * (int64_t)device_cu_count();
-    const unsigned nb = (unsigned)(want < cap ? want : cap);
+    const unsigned nb = point_grid(N, 2);                                  // (k_char_app flushes dW per workgroup)
     hipLaunchKernelGGL(k_char_density, dim3(nb), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_char_app, dim3(nb), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_char_finish, dim3(1), dim3(64), 0, st, P.acc, 1.0 / (double)N, 1.0 / ((double)N * (double)f->app_dim), loss);

@@ -6,7 +6,7 @@
 //            order-preserving 32-bit keys: 4 passes of 8 bits, both maps in the same pass.  Histograms live in LDS (4 copies per map, waves
 //            w, w + 4, .. share one); a wave first folds the lanes that share the bin of its leading lanes into one add (depth maps have
 //            plateaus: every ray that hits nothing has depth == far), the rest add singly.  Counts are integers: order cannot change them.
-//   sums     two passes of fp64 sums (tie count, both deviations | loss, A, B, sum of signs) reduced wave -> workgroup in a fixed order, so two
+//   sums     two passes of fp64 sums (tie count, both deviations | loss, A, B, sum of signs) reduced wave -> workgroup in a fixed order (reduce.h), so two
 //            calls on the same input give the same bits; per-entry arithmetic is fp64 too, the results are rounded to fp32 once.
 //   gradient torch's full-tensor median spreads its gradient equally over all entries EQUAL to the median (float compare: -0.0 == +0.0):
 //            e_j = [p_j == med] / c,  a_j = 2 (u_j - v_j) / n_c,  A = sum a_j,  B = sum a_j (p_j - med),  sg_j = sign(p_j - med)
@@ -14,7 +14,7 @@
 //   memory   n <= NVFI_DEPTH_LDS_MAX: both maps are read once and kept in LDS (2 x 4 n bytes, up to 128 KiB + 8.5 KiB of histograms and
 //            partial sums); above, every pass streams them from global memory (a 640 000-entry frame is 5 MB: it stays in L2).
 // No global atomics, no memset, no host synchronisation: the call can be captured in a hipGraph.
-#include "common.h"
+#include "reduce.h"
 
 #define DL_THREADS 1024
 #define DL_WAVES (DL_THREADS / 64)
@@ -81,25 +81,6 @@ __device__ __forceinline__ void dl_select(unsigned* hist, unsigned* st, int shif
     }
 }
 
-// sums DL_NSUM doubles over the workgroup: wave butterflies, then every thread adds the 16 wave sums in the same order
-__device__ __forceinline__ void dl_block_sum(double* v, double* part, int lane, int wave) {
-#pragma unroll
-    for (int q = 0; q < DL_NSUM; ++q)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o);
-    __syncthreads();                                  // (the previous round's readers are done with `part`)
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < DL_NSUM; ++q) part[wave * DL_NSUM + q] = v[q];
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < DL_NSUM; ++q) {
-        double s = 0.0;
-        for (int w = 0; w < DL_WAVES; ++w) s += part[w * DL_NSUM + q];
-        v[q] = s;
-    }
-}
-
 template <bool IN_LDS>
 __global__ __launch_bounds__(DL_THREADS) void k_depth_loss(int64_t n, const float* __restrict__ pred, const float* __restrict__ gt,
                                                            const int64_t* __restrict__ gt_index, int flags, float grad_scale,
@@ -163,7 +144,7 @@ __global__ __launch_bounds__(DL_THREADS) void k_depth_loss(int64_t n, const floa
         v[1] += fabs((double)p - (double)med_p);
         v[2] += fabs((double)g - (double)med_g);
     }
-    dl_block_sum(v, part, lane, wave);
+    block_sum_ordered<DL_WAVES, DL_NSUM>(v, part, lane, wave);
     const double ties = v[0];
     const double inv_p = 1.0 / (v[1] * inv_n + 1e-6), inv_g = 1.0 / (v[2] * inv_n + 1e-6);
 
@@ -180,7 +161,7 @@ __global__ __launch_bounds__(DL_THREADS) void k_depth_loss(int64_t n, const floa
         v[2] += d * dp;
         v[3] += dp > 0.0 ? 1.0 : (dp < 0.0 ? -1.0 : 0.0);
     }
-    dl_block_sum(v, part, lane, wave);
+    block_sum_ordered<DL_WAVES, DL_NSUM>(v, part, lane, wave);
     const double A = 2.0 * inv_n * v[1], B = 2.0 * inv_n * v[2], sum_sg = v[3];
     if (tid == 0) {
         *loss = (float)(v[0] * inv_n);

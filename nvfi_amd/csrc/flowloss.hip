@@ -9,14 +9,14 @@
 //   launch_rk2_x6     Phi(x_j) = integrate_pos(x_j, t, t + dt), the no-grad per-point integrator of nvfi_integrate_pos / nvfi_render_flow, in place
 //   / launch_rk2_fwd
 //   k_fl_ray          one wave per ray, lanes as in k_flow_final: flow2d[r] as an ordered sum, the error against the target, the ray's loss term (fp64)
-//   k_fl_mean         ONE workgroup: the valid count n and the mean in a fixed order (raydist.hip's scheme)
+//   k_fl_mean         ONE workgroup: the valid count n and the mean in a fixed order (reduce.h's ordered workgroup sum)
 //   k_fl_grad         one thread per masked entry: g_weights (written behind a zero fill, or added to) and g_xd, the gradient at the displaced point
 // nvfi_flow_loss_bwd handles the entries [first, first + chunk_cap) of the masked list, clipped on the device:
 //   k_fl_pack         the chunk's dense positions, g_xd, the identity list, the device count
 //   advect_chain      the chain of nvfi_advect_grad (advect.h): stash-writing uniform warp, unfused adjoint, weight-gradient jobs
 // No MFMA code is instantiated here, no host synchronisation, no float atomics of its own: two calls repeat bit for bit.
 #include <string.h>
-#include "common.h"
+#include "reduce.h"
 #include "render.h"
 #include "vel.h"
 #include "x6.h"
@@ -165,13 +165,7 @@ __global__ __launch_bounds__(256) void k_fl_ray(FlArgs a) {
     }
 }
 
-__device__ __forceinline__ double fl_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// n = number of valid rays, loss = sum of the per-ray terms / (2 n): every thread sums its stride, waves fold by butterflies, thread 0 adds the 16
-// wave sums in order
+// n = number of valid rays, loss = sum of the per-ray terms / (2 n): every thread sums its stride, then the workgroup's ordered sums (reduce.h)
 __global__ __launch_bounds__(FL_MEAN_THREADS) void k_fl_mean(FlArgs a) {
     __shared__ double part[FL_MEAN_THREADS / 64];
     __shared__ int npart[FL_MEAN_THREADS / 64];
@@ -179,17 +173,11 @@ __global__ __launch_bounds__(FL_MEAN_THREADS) void k_fl_mean(FlArgs a) {
     double s = 0.0;
     int n = 0;
     for (int64_t i = tid; i < a.R; i += FL_MEAN_THREADS) { s += a.lterm[i]; n += a.vflag[i]; }
-    s = fl_wave_sum(s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-    if ((tid & 63) == 0) { part[tid >> 6] = s; npart[tid >> 6] = n; }
-    __syncthreads();
+    block_sum_ordered<FL_MEAN_THREADS / 64, 1>(&s, part, tid & 63, tid >> 6);
+    block_sum_ordered<FL_MEAN_THREADS / 64, 1>(&n, npart, tid & 63, tid >> 6);
     if (tid == 0) {
-        double t = 0.0;
-        int nn = 0;
-        for (int k = 0; k < FL_MEAN_THREADS / 64; ++k) { t += part[k]; nn += npart[k]; }
-        a.hdr[1] = nn;
-        if (a.loss) { a.loss[0] = nn > 0 ? (float)(t / (2.0 * (double)nn)) : 0.f; a.loss[1] = (float)nn; }
+        a.hdr[1] = n;
+        if (a.loss) { a.loss[0] = n > 0 ? (float)(s / (2.0 * (double)n)) : 0.f; a.loss[1] = (float)n; }
     }
 }
 

@@ -7,16 +7,13 @@
 // four weights - so the value and both gradients see the same cell as nvfi_density_at.  Nothing is stashed: the backward reads the taps again,
 // forms each plane's share as upstream x the product of the other five bilinear values and adds it to the four texels; the coordinate
 // gradient is ATen's grid_sampler_2d_backward (the difference of the in-range taps times (W - 1) / 2, (H - 1) / 2, and (K - 1) / 2 for t').
-// Lane layout as in charloss.hip - one wave per point in a grid-stride loop, lanes are CHANNELS, per-point quantities are wave-uniform:
-//   density (24 channels)  lane = 2 * channel + x-tap: one load / atomic instruction covers two neighbouring texels (192 B); 12 per point = 2304 B
-//   appearance (48)        lane = channel: one texel per instruction (192 B); 24 per point = 4608 B
-// basis_mat (app_dim x 48) sits in LDS with an odd row stride; per point one lane per channel forms W^T g_feat, and dW = sum g_feat prod^T is
-// kept in registers per wave (lane = column), reduced per workgroup in LDS, and only then added to global memory.
+// One wave per point, lanes are channels, per-point quantities are wave-uniform (pointwave.h: the lane layouts, the tap sets, basis_mat in LDS, the
+// dW flush).  Per point the density adjoint issues 12 tap instructions = 2304 B, the appearance kernels 24 = 4608 B.
 // g_xyzt and feat are plain stores, folded over the lanes with a fixed butterfly: they repeat bit for bit.  The plane and basis_mat gradients
 // are float atomics into buffers the caller zeroed: they do NOT repeat bit for bit and are not covered by NVFI_DETERMINISTIC.
 // No workspace, no clearing, no allocation, no host wait: every call is a single launch on `stream` and can be captured in a hipGraph.
 #include <string.h>
-#include "common.h"
+#include "pointwave.h"
 #include "render.h"
 
 struct LookArgs {
@@ -29,29 +26,14 @@ struct LookArgs {
     float* feat;           // (N, app_dim): the appearance forward
 };
 
-__device__ __forceinline__ float look_uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ float look_bcast(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
 // the six tap sets of a point (wave-uniform).  A plane none of whose taps is in range gets zero weights: a non-finite coordinate leaves NaN in
 // them, and the coordinate gradient multiplies weights with (zeroed) taps.  A plane with a tap in range has finite weights on both axes.
 __device__ __forceinline__ void look_setups(const nvfi_field_desc& f, const float* q, Bl* b) {
     const float4 p = ld4(q);
-    plane_setups(f, look_uni(p.x), look_uni(p.y), look_uni(p.z), look_uni(p.w), b);
+    plane_setups(f, uni(p.x), uni(p.y), uni(p.z), uni(p.w), b);
 #pragma unroll
     for (int i = 0; i < 6; ++i)
         if (!(b[i].m0 || b[i].m1 || b[i].m2 || b[i].m3)) { b[i].w = 0.f; b[i].e = 0.f; b[i].n = 0.f; b[i].s = 0.f; }
-}
-// upstream x the product of the other five values
-__device__ __forceinline__ void other_five(const float* val, float g, float* o) {
-    float L[6], R[6];
-    L[0] = g;
-#pragma unroll
-    for (int p = 1; p < 6; ++p) L[p] = L[p - 1] * val[p - 1];
-    R[5] = 1.f;
-#pragma unroll
-    for (int p = 4; p >= 0; --p) R[p] = R[p + 1] * val[p + 1];
-#pragma unroll
-    for (int p = 0; p < 6; ++p) o[p] = L[p] * R[p];
 }
 // routing of the per-plane texel-coordinate gradients (gx[p], gy[p], p = space 0..2, time 3..5) to x, y, z, t' (matModeSpace / matModeTime),
 // summed over the wave and scaled by (G - 1) / 2 resp. (K - 1) / 2; lane l < 4 stores component l
@@ -67,38 +49,39 @@ __device__ __forceinline__ void coord_store(const nvfi_field_desc& f, const floa
     if (lane < 4) out[lane] = r;
 }
 
-// ---------------------------------------------------------------- density: lane = 2 * channel + x-tap
+// Loads here are UNCONDITIONAL and then selected (the taps of all six planes are in flight together): a masked tap reads texel 0, so its offset -
+// and ch in the idle lanes - is clamped to 0 before the load.  (charloss.hip loads under the mask and never clamps.)
+template <int NT> __device__ __forceinline__ void clamp_taps(LaneTaps<NT>& t) {
+#pragma unroll
+    for (int k = 0; k < NT; ++k) t.o[k] = t.m[k] ? t.o[k] : 0;
+}
+
+// ---------------------------------------------------------------- density
 __global__ __launch_bounds__(256) void k_lookup_density_bwd(LookArgs a) {
     const nvfi_field_desc& f = a.f;
-    const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-    const int64_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * nwv + (threadIdx.x >> 6)), wtot = (int64_t)gridDim.x * nwv;
+    const PointWalk w;
+    const int lane = w.lane;
     const bool lane_on = lane < 48;
     const int ch = lane_on ? lane >> 1 : 0, dx0 = lane & 1;
     const float* pl[6]; float* gp[6];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { pl[p] = f.dps[p]; pl[3 + p] = f.dpt[p]; gp[p] = a.g.dps[p]; gp[3 + p] = a.g.dpt[p]; }
+    family_planes(f.dps, f.dpt, pl);
+    family_planes(a.g.dps, a.g.dpt, gp);
 #pragma unroll 1
-    for (int64_t n = wave0; n < a.N; n += wtot) {
+    for (int64_t n = w.wave0; n < a.N; n += w.wtot) {
         Bl b[6];
         look_setups(f, a.q + 4 * n, b);
-        const float g = look_uni(a.gf[n]);
+        const float g = uni(a.gf[n]);
         float val[6], dx[6], dy[6], wx[6];
-        size_t o0[6], o1[6];
-        bool my0[6], my1[6];
+        LaneTaps<2> t[6];
 #pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            my0[p] = lane_on && (dx0 ? b[p].m1 : b[p].m0); my1[p] = lane_on && (dx0 ? b[p].m3 : b[p].m2);
-            wx[p] = dx0 ? b[p].w : b[p].e;
-            o0[p] = my0[p] ? (size_t)(b[p].base + dx0) * 24 + ch : 0;                  // a masked tap reads texel 0 and is zeroed by a select
-            o1[p] = my1[p] ? (size_t)(b[p].base + dx0 + b[p].W) * 24 + ch : 0;
-        }
+        for (int p = 0; p < 6; ++p) { density_taps(b[p], ch, dx0, lane_on, t[p], wx[p]); clamp_taps(t[p]); }
         float v0[6], v1[6];
 #pragma unroll
-        for (int p = 0; p < 6; ++p) { v0[p] = pl[p][o0[p]]; v1[p] = pl[p][o1[p]]; }
+        for (int p = 0; p < 6; ++p) { v0[p] = pl[p][t[p].o[0]]; v1[p] = pl[p][t[p].o[1]]; }
 #pragma unroll
         for (int p = 0; p < 6; ++p) {
-            v0[p] = my0[p] ? v0[p] : 0.f; v1[p] = my1[p] ? v1[p] : 0.f;
-            const float part = v0[p] * (wx[p] * b[p].s) + v1[p] * (wx[p] * b[p].n);
+            v0[p] = t[p].m[0] ? v0[p] : 0.f; v1[p] = t[p].m[1] ? v1[p] : 0.f;
+            const float part = v0[p] * t[p].w[0] + v1[p] * t[p].w[1];
             val[p] = part + __shfl_xor(part, 1);                                        // both lanes of a pair: the channel's bilinear value
             const float row = v0[p] * b[p].s + v1[p] * b[p].n;
             dx[p] = dx0 ? row : -row;                                                   // d value / d texel-x: this lane's x-tap
@@ -112,25 +95,16 @@ __global__ __launch_bounds__(256) void k_lookup_density_bwd(LookArgs a) {
             coord_store(f, dx, dy, lane, a.gq + 4 * n);
         }
 #pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            if (!gp[p]) continue;
-            if (my0[p]) atomicAdd(gp[p] + o0[p], (wx[p] * b[p].s) * o[p]);
-            if (my1[p]) atomicAdd(gp[p] + o1[p], (wx[p] * b[p].n) * o[p]);
-        }
+        for (int p = 0; p < 6; ++p)
+            if (gp[p]) scatter_taps(gp[p], t[p], o[p]);
     }
 }
 
-// ---------------------------------------------------------------- appearance: lane = channel (48 of 64 lanes)
-struct AppTaps { size_t o[4]; bool m[4]; };
-__device__ __forceinline__ void app_taps(const Bl& b, int ch, bool lane_on, AppTaps& t) {
-    t.m[0] = lane_on && b.m0; t.m[1] = lane_on && b.m1; t.m[2] = lane_on && b.m2; t.m[3] = lane_on && b.m3;
-    t.o[0] = t.m[0] ? (size_t)b.base * 48 + ch : 0;
-    t.o[1] = t.m[1] ? (size_t)(b.base + 1) * 48 + ch : 0;
-    t.o[2] = t.m[2] ? (size_t)(b.base + b.W) * 48 + ch : 0;
-    t.o[3] = t.m[3] ? (size_t)(b.base + b.W + 1) * 48 + ch : 0;
-}
+// ---------------------------------------------------------------- appearance
 // the six bilinear values of this lane's channel (0 in lanes >= 48); v keeps the zero-padded taps
-__device__ __forceinline__ void app_vals(const float* const* pl, const Bl* b, const AppTaps* t, float (*v)[4], float* val) {
+__device__ __forceinline__ void app_vals(const float* const* pl, const Bl* b, int ch, bool lane_on, LaneTaps<4>* t, float (*v)[4], float* val) {
+#pragma unroll
+    for (int p = 0; p < 6; ++p) { app_taps(b[p], ch, lane_on, t[p]); clamp_taps(t[p]); }
 #pragma unroll
     for (int p = 0; p < 6; ++p)
 #pragma unroll
@@ -139,83 +113,67 @@ __device__ __forceinline__ void app_vals(const float* const* pl, const Bl* b, co
     for (int p = 0; p < 6; ++p) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[p][k] = t[p].m[k] ? v[p][k] : 0.f;
-        val[p] = v[p][0] * (b[p].e * b[p].s) + v[p][1] * (b[p].w * b[p].s) + v[p][2] * (b[p].e * b[p].n) + v[p][3] * (b[p].w * b[p].n);
+        val[p] = v[p][0] * t[p].w[0] + v[p][1] * t[p].w[1] + v[p][2] * t[p].w[2] + v[p][3] * t[p].w[3];
     }
-}
-__device__ __forceinline__ float prod6(const float* v) { return ((v[0] * v[1]) * v[2]) * ((v[3] * v[4]) * v[5]); }
-
-#define LK_WSTRIDE 49      // LDS row stride of basis_mat: odd, so lanes that read a column (row = lane) hit 32 different banks
-__device__ __forceinline__ void stage_basis(const nvfi_field_desc& f, float* Wl, float* red) {
-    for (int k = threadIdx.x; k < 32 * 48; k += blockDim.x) {
-        const int j = k / 48, c = k - 48 * j;
-        Wl[j * LK_WSTRIDE + c] = j < f.app_dim ? f.basis[k] : 0.f;      // rows >= app_dim zero
-        if (red) red[k] = 0.f;
-    }
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(256) void k_lookup_app_fwd(LookArgs a) {
-    __shared__ float Wl[32 * LK_WSTRIDE];
+    __shared__ float Wl[32 * PW_WSTRIDE];
     const nvfi_field_desc& f = a.f;
-    const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-    const int64_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * nwv + (threadIdx.x >> 6)), wtot = (int64_t)gridDim.x * nwv;
+    const PointWalk w;
+    const int lane = w.lane;
     const bool lane_on = lane < 48;
     const int ch = lane_on ? lane : 0, jrow = lane & 31;
     const int app_dim = f.app_dim;
     stage_basis(f, Wl, nullptr);
     const float* pl[6];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { pl[p] = f.aps[p]; pl[3 + p] = f.apt[p]; }
+    family_planes(f.aps, f.apt, pl);
 #pragma unroll 1
-    for (int64_t n = wave0; n < a.N; n += wtot) {
+    for (int64_t n = w.wave0; n < a.N; n += w.wtot) {
         Bl b[6];
         look_setups(f, a.q + 4 * n, b);
-        AppTaps t[6];
-#pragma unroll
-        for (int p = 0; p < 6; ++p) app_taps(b[p], ch, lane_on, t[p]);
+        LaneTaps<4> t[6];
         float v[6][4], val[6];
-        app_vals(pl, b, t, v, val);
+        app_vals(pl, b, ch, lane_on, t, v, val);
         const float pr = prod6(val);
         float y = 0.f;                                                     // lane j < app_dim: (W prod)_j
 #pragma unroll 8
-        for (int c = 0; c < 48; ++c) y += Wl[jrow * LK_WSTRIDE + c] * look_bcast(pr, c);
+        for (int c = 0; c < 48; ++c) y += Wl[jrow * PW_WSTRIDE + c] * lane_bcast(pr, c);
         if (lane < app_dim) a.feat[n * app_dim + lane] = y;
     }
 }
 
 __global__ __launch_bounds__(256) void k_lookup_app_bwd(LookArgs a) {
-    __shared__ float Wl[32 * LK_WSTRIDE];      // basis_mat
+    __shared__ float Wl[32 * PW_WSTRIDE];      // basis_mat
     __shared__ float red[32 * 48];             // dW of the workgroup
     const nvfi_field_desc& f = a.f;
-    const int lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
-    const int64_t wave0 = __builtin_amdgcn_readfirstlane(blockIdx.x * nwv + (threadIdx.x >> 6)), wtot = (int64_t)gridDim.x * nwv;
+    const PointWalk w;
+    const int lane = w.lane;
     const bool lane_on = lane < 48;
     const int ch = lane_on ? lane : 0;
     const int app_dim = f.app_dim;
     stage_basis(f, Wl, red);
     const float* pl[6]; float* gp[6];
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { pl[p] = f.aps[p]; pl[3 + p] = f.apt[p]; gp[p] = a.g.aps[p]; gp[3 + p] = a.g.apt[p]; }
+    family_planes(f.aps, f.apt, pl);
+    family_planes(a.g.aps, a.g.apt, gp);
     const bool want_w = a.g.basis != nullptr;
     float accW[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) accW[j] = 0.f;
 #pragma unroll 1
-    for (int64_t n = wave0; n < a.N; n += wtot) {
+    for (int64_t n = w.wave0; n < a.N; n += w.wtot) {
         Bl b[6];
         look_setups(f, a.q + 4 * n, b);
-        AppTaps t[6];
-#pragma unroll
-        for (int p = 0; p < 6; ++p) app_taps(b[p], ch, lane_on, t[p]);
         const float gfv = lane < app_dim ? a.gf[n * app_dim + lane] : 0.f;  // lane j: g_feat[j]
+        LaneTaps<4> t[6];
         float v[6][4], val[6];
-        app_vals(pl, b, t, v, val);
+        app_vals(pl, b, ch, lane_on, t, v, val);
         const float pr = prod6(val);
         float gl = 0.f;                                                     // lane c < 48: (W^T g_feat)_c
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
-            const float gj = look_bcast(gfv, j);
-            gl += Wl[j * LK_WSTRIDE + ch] * gj;
+            const float gj = lane_bcast(gfv, j);
+            gl += Wl[j * PW_WSTRIDE + ch] * gj;
             if (want_w) accW[j] += gj * pr;
         }
         if (!lane_on) gl = 0.f;
@@ -231,33 +189,14 @@ __global__ __launch_bounds__(256) void k_lookup_app_bwd(LookArgs a) {
             coord_store(f, dx, dy, lane, a.gq + 4 * n);
         }
 #pragma unroll
-        for (int p = 0; p < 6; ++p) {
-            if (!gp[p]) continue;
-            if (t[p].m[0]) atomicAdd(gp[p] + t[p].o[0], (b[p].e * b[p].s) * o[p]);
-            if (t[p].m[1]) atomicAdd(gp[p] + t[p].o[1], (b[p].w * b[p].s) * o[p]);
-            if (t[p].m[2]) atomicAdd(gp[p] + t[p].o[2], (b[p].e * b[p].n) * o[p]);
-            if (t[p].m[3]) atomicAdd(gp[p] + t[p].o[3], (b[p].w * b[p].n) * o[p]);
-        }
+        for (int p = 0; p < 6; ++p)
+            if (gp[p]) scatter_taps(gp[p], t[p], o[p]);
     }
-    if (want_w) {
-        if (lane_on) {
-#pragma unroll
-            for (int j = 0; j < 32; ++j)
-                if (accW[j] != 0.f) atomicAdd(&red[j * 48 + ch], accW[j]);
-        }
-        __syncthreads();
-        for (int k = threadIdx.x; k < app_dim * 48; k += blockDim.x)
-            if (red[k] != 0.f) atomicAdd(a.g.basis + k, red[k]);
-    }
+    if (want_w) flush_dw(accW, red, ch, lane_on, app_dim, 1.f, a.g.basis);
 }
 
 // ---------------------------------------------------------------- host
 static const int64_t LOOKUP_N_MAX = (1ll << 31) - 256;       // nvfi_density_at's limit
-// a wave walks the points with a grid stride: at least four points per wave, at most `per_cu` workgroups per CU
-static unsigned lookup_grid(int64_t N, int per_cu) {
-    const int64_t want = (N + 15) / 16, cap = (int64_t)per_cu * device_cu_count();
-    return (unsigned)(want < cap ? want : cap);
-}
 static int lookup_check(const char* name, const nvfi_field_desc* f, int64_t N, const float* xyzt, const void* other) {
     if (check_desc(f)) return 2;
     if (N <= 0) return -1;
@@ -275,7 +214,7 @@ extern "C" int nvfi_density_grad(const nvfi_field_desc* f, int64_t N, const floa
     if (grads)
         for (int i = 0; i < 3; ++i) { a.g.dps[i] = grads->dps[i]; a.g.dpt[i] = grads->dpt[i]; any = any || grads->dps[i] || grads->dpt[i]; }
     if (!any) return 0;
-    hipLaunchKernelGGL(k_lookup_density_bwd, dim3(lookup_grid(N, 8)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_lookup_density_bwd, dim3(point_grid(N, 8)), dim3(256), 0, (hipStream_t)stream, a);
     LAUNCHCK();
     return 0;
 }
@@ -283,7 +222,7 @@ extern "C" int nvfi_appfeat_at(const nvfi_field_desc* f, int64_t N, const float*
     if (const int rc = lookup_check("nvfi_appfeat_at", f, N, xyzt, feat)) return rc < 0 ? 0 : rc;
     LookArgs a; memset(&a, 0, sizeof(a));
     a.f = *f; a.N = N; a.q = xyzt; a.feat = feat;
-    hipLaunchKernelGGL(k_lookup_app_fwd, dim3(lookup_grid(N, 8)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_lookup_app_fwd, dim3(point_grid(N, 8)), dim3(256), 0, (hipStream_t)stream, a);
     LAUNCHCK();
     return 0;
 }
@@ -298,8 +237,7 @@ extern "C" int nvfi_appfeat_grad(const nvfi_field_desc* f, int64_t N, const floa
         a.g.basis = grads->basis; any = any || grads->basis;
     }
     if (!any) return 0;
-    // at most four workgroups per CU, so that the per-workgroup flush of dW stays a small share
-    hipLaunchKernelGGL(k_lookup_app_bwd, dim3(lookup_grid(N, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_lookup_app_bwd, dim3(point_grid(N, 4)), dim3(256), 0, (hipStream_t)stream, a);      // (flushes dW per workgroup)
     LAUNCHCK();
     return 0;
 }

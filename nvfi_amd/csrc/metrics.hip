@@ -13,13 +13,11 @@
 // Arithmetic: the windowed moments are second moments whose differences (E[x^2] - mu^2) cancel; both passes therefore accumulate in fp64 (fp32
 // products are exact there), and the SSIM formula is evaluated in fp64.  The per-pixel work is ~130 fp64 FMAs, a few tens of microseconds per
 // 800 x 800 x 3 frame: the kernel stays bound by its launches.
-// House rules (segloss.hip): every clear is a kernel, nothing waits for the device, no float atomic on a result, partials are summed by the last
-// workgroup in a fixed order in fp64 - the results do not depend on which workgroup came last and repeat bit for bit.
+// House rules and the in-launch hand-off (publish, last_arrival, read_published): reduce.h - the results repeat bit for bit.
 #include <limits.h>
 #include <string.h>
-#include "common.h"
+#include "reduce.h"
 
-#define MET_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 #define MET_WGS 256              // workgroups per frame of the grid-stride kernels (= partials per value)
 #define MET_MAX_K 32
 #define MET_MAX_G 32
@@ -30,29 +28,13 @@
 #define SSIM_IW (SSIM_TW + SSIM_W - 1)
 #define SSIM_IH (SSIM_TH + SSIM_W - 1)
 
-__device__ __forceinline__ void met_publish(double* p, double v) { __hip_atomic_store((long long*)p, __double_as_longlong(v), MET_RLX); }
-__device__ __forceinline__ double met_read(const double* p) { return __longlong_as_double(__hip_atomic_load((const long long*)p, MET_RLX)); }
-__device__ __forceinline__ void met_publish_f(float* p, float v) { __hip_atomic_store(p, v, MET_RLX); }
-__device__ __forceinline__ float met_read_f(const float* p) { return __hip_atomic_load(p, MET_RLX); }
-// every thread of the workgroup, after its publishes: true in the workgroup that is the `total`-th to arrive at this ticket
-__device__ __forceinline__ bool met_arrive(int* ticket, int total) {
-    __shared__ bool last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(ticket, 1, MET_RLX) == total - 1;
-    __syncthreads();
-    return last;
-}
-__device__ __forceinline__ double met_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// sum of n partials at p[i * stride] by the whole workgroup (256 threads) in a fixed order: thread t takes i = t, t + 256, ...; wave tree; waves 0..3
+// sum of n partials at p[i * stride] by the whole workgroup (256 threads) in a fixed order: thread t takes i = t, t + 256, ...; wave tree; waves 0..3.
+// Not reduce.h's block_sum_ordered: the four wave sums are added PAIRWISE (as in the publishes of k_ssim and k_segm_confusion) - the sequential
+// order gives other bits
 __device__ __forceinline__ double met_block_sum(const double* p, int64_t n, int64_t stride, double* red4) {
     double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) s += met_read(p + i * stride);
-    s = met_wave_sum(s);
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += read_published(p + i * stride);
+    s = wave_sum(s);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -96,15 +78,15 @@ __global__ __launch_bounds__(256) void k_ssim_range(SsimArgs a) {
     if (lane == 0) { red[wv][0] = lo; red[wv][1] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        met_publish_f(a.rpart + ((int64_t)b * gridDim.x + blockIdx.x) * 2, fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0])));
-        met_publish_f(a.rpart + ((int64_t)b * gridDim.x + blockIdx.x) * 2 + 1, fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1])));
+        publish(a.rpart + ((int64_t)b * gridDim.x + blockIdx.x) * 2, fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0])));
+        publish(a.rpart + ((int64_t)b * gridDim.x + blockIdx.x) * 2 + 1, fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1])));
     }
-    if (!met_arrive(a.tickets + a.B + b, (int)gridDim.x)) return;
+    if (!last_arrival(a.tickets + a.B + b, (int)gridDim.x)) return;
     if (wv == 0) {
         lo = INFINITY; hi = -INFINITY;
         for (int w = lane; w < (int)gridDim.x; w += 64) {
-            lo = fminf(lo, met_read_f(a.rpart + ((int64_t)b * gridDim.x + w) * 2));
-            hi = fmaxf(hi, met_read_f(a.rpart + ((int64_t)b * gridDim.x + w) * 2 + 1));
+            lo = fminf(lo, read_published(a.rpart + ((int64_t)b * gridDim.x + w) * 2));
+            hi = fmaxf(hi, read_published(a.rpart + ((int64_t)b * gridDim.x + w) * 2 + 1));
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o)); hi = fmaxf(hi, __shfl_xor(hi, o)); }
@@ -173,13 +155,13 @@ __global__ __launch_bounds__(256) void k_ssim(SsimArgs a) {
         acc_c += v1 / v2;
         acc_s += ((2.0 * mu12 + C1) * v1) / ((mu11 + mu22 + C1) * v2);
     }
-    acc_s = met_wave_sum(acc_s); acc_c = met_wave_sum(acc_c);
+    acc_s = wave_sum(acc_s); acc_c = wave_sum(acc_c);
     if (lane == 0) { red[wv][0] = acc_s; red[wv][1] = acc_c; }
     __syncthreads();
     const int64_t per_image = (int64_t)a.C * gridDim.x;
     double* part = a.part + ((int64_t)b * per_image + (int64_t)c * gridDim.x + tile) * 2;
-    if (threadIdx.x < 2) met_publish(part + threadIdx.x, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
-    if (!met_arrive(a.tickets + b, (int)per_image)) return;
+    if (threadIdx.x < 2) publish(part + threadIdx.x, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+    if (!last_arrival(a.tickets + b, (int)per_image)) return;
     const double cnt = (double)a.C * (double)(a.H - (SSIM_W - 1)) * (double)(a.W - (SSIM_W - 1));
     const double* base = a.part + (int64_t)b * per_image * 2;
     const double s = met_block_sum(base, per_image, 2, red4);
@@ -245,7 +227,7 @@ __global__ __launch_bounds__(256) void k_segm_confusion(ConfArgs a) {
             const int leader = __ffsll((long long)todo) - 1;
             const int lp = __shfl(pair, leader);
             const unsigned long long same = __ballot(pair == lp);
-            const double cs = met_wave_sum(pair == lp ? conf : 0.0);
+            const double cs = wave_sum(pair == lp ? conf : 0.0);
             if (lane == leader) { atomicAdd(&hist[lp], __popcll(same)); wconf[wv][lp % a.K] += cs; }
             todo &= ~same;
         }
@@ -256,15 +238,15 @@ __global__ __launch_bounds__(256) void k_segm_confusion(ConfArgs a) {
         if (hist[i]) atomicAdd(a.counts + (int64_t)b * cells + i, (unsigned long long)hist[i]);
     if (threadIdx.x == 0 && sbad) atomicAdd(a.badws + b, sbad);
     double* part = a.part + ((int64_t)b * gridDim.x + blockIdx.x) * MET_MAX_K;
-    if ((int)threadIdx.x < a.K) { const int c = threadIdx.x; met_publish(part + c, (wconf[0][c] + wconf[1][c]) + (wconf[2][c] + wconf[3][c])); }
-    if (!met_arrive(a.tickets + b, (int)gridDim.x)) return;
+    if ((int)threadIdx.x < a.K) { const int c = threadIdx.x; publish(part + c, (wconf[0][c] + wconf[1][c]) + (wconf[2][c] + wconf[3][c])); }
+    if (!last_arrival(a.tickets + b, (int)gridDim.x)) return;
     if ((int)threadIdx.x < a.K) {
         const int c = threadIdx.x;
         double s = 0.0;
-        for (int w = 0; w < (int)gridDim.x; ++w) s += met_read(a.part + ((int64_t)b * gridDim.x + w) * MET_MAX_K + c);
+        for (int w = 0; w < (int)gridDim.x; ++w) s += read_published(a.part + ((int64_t)b * gridDim.x + w) * MET_MAX_K + c);
         a.conf_sum[(int64_t)b * a.K + c] = s;
     }
-    if (threadIdx.x == 0) a.bad[b] = __hip_atomic_load(a.badws + b, MET_RLX);
+    if (threadIdx.x == 0) a.bad[b] = __hip_atomic_load(a.badws + b, RED_RLX);
 }
 
 // ---------------------------------------------------------------- host

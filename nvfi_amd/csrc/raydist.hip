@@ -11,15 +11,9 @@
 //              registers, a ray of 1024 samples is 16 chunks of w and A per lane and S gets a cap).  g_weights must not overlap weights.
 // k_ray_mean   second launch of ONE workgroup over the R fp64 per-ray values in the workspace, summed in a fixed order: two calls give the same bits.
 // No LDS in the scans, no atomics, no memset, no host synchronisation: the call can be captured in a hipGraph.
-#include "common.h"
+#include "reduce.h"
 
 #define RD_MEAN_THREADS 1024
-
-__device__ __forceinline__ double rd_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_ray_dist(int64_t R, int S, const float* __restrict__ weights, float delta, float grad_scale,
                                                   const float* __restrict__ grad_scale_dev, double inv_R, double* __restrict__ dr,
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void k_ray_dist(int64_t R, int S, const float*
         if (g && j < S) g[j] = k2 * A + k23 * x;       // the left half of the gradient; the reverse sweep's SAME lane adds the right half
     }
     if (dr || per_ray) {
-        s1 = rd_wave_sum(s1); s2 = rd_wave_sum(s2);
+        s1 = wave_sum(s1); s2 = wave_sum(s2);
         if (lane == 0) {
             const double D = (double)delta * (2.0 * s1 + s2 / 3.0);
             if (dr) dr[r] = D;
@@ -82,20 +76,14 @@ __global__ __launch_bounds__(256) void k_ray_dist(int64_t R, int S, const float*
     }
 }
 
-// loss[0] = inv_R * sum of dr[0..R): every thread sums its stride, waves fold by butterflies, thread 0 adds the 16 wave sums in order
+// loss[0] = inv_R * sum of dr[0..R): every thread sums its stride, then the workgroup's ordered sum (reduce.h)
 __global__ __launch_bounds__(RD_MEAN_THREADS) void k_ray_mean(int64_t R, const double* __restrict__ dr, double inv_R, float* __restrict__ loss) {
     __shared__ double part[RD_MEAN_THREADS / 64];
     const int tid = threadIdx.x;
     double s = 0.0;
     for (int64_t i = tid; i < R; i += RD_MEAN_THREADS) s += dr[i];
-    s = rd_wave_sum(s);
-    if ((tid & 63) == 0) part[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int k = 0; k < RD_MEAN_THREADS / 64; ++k) t += part[k];
-        loss[0] = (float)(t * inv_R);
-    }
+    block_sum_ordered<RD_MEAN_THREADS / 64, 1>(&s, part, tid & 63, tid >> 6);
+    if (tid == 0) loss[0] = (float)(s * inv_R);
 }
 
 static int64_t rd_workspace_bytes(int64_t R) { return align_up((R > 0 ? R : 1) * (int64_t)sizeof(double), 256); }

@@ -14,14 +14,10 @@
 //                                     order in fp64 and runs the K 3x3 SVDs (one-sided Jacobi, fp64, one lane each) -> R, t
 //                   k_seg_points      one thread per point: q = sum_k m_k (R_k pc + t_k), the three loss terms and the whole row of d/d mask
 //                                     (both ends of every kNN edge through the reverse lists: a gather, no float atomics); losses in two stages
-// Every clear is a kernel (launch_zero), nothing waits for the device, every launch is on the caller's stream.
-//
-// In-launch hand-off (the project's ticket pattern, render_rays.hip k_final_fwd): partial sums are agent-scope atomic stores, every storing wave
-// drains them (s_waitcnt vmcnt(0)) before the workgroup's barrier, one lane then draws the ticket; the last workgroup reads the partials with
-// agent-scope atomic loads, in workgroup order, so the value does not depend on which workgroup came last.  Tickets are zero at launch.
+// House rules and the in-launch hand-off (publish, last_arrival, read_published): reduce.h.  Every ticket here counts the launch's gridDim.x workgroups.
 #include <limits.h>
 #include <string.h>
-#include "common.h"
+#include "reduce.h"
 
 #define SEG_MAX_CELLS 65536      // cap of the cell grid: beyond it the cell side grows (the search stays exact, it only visits more points)
 #define SEG_MAX_AXIS 256         // cells per axis: cell coordinates stay far below the 2^-24 relative rounding of their computation
@@ -32,23 +28,6 @@
 
 struct SegGrid { float lo[3]; float inv; int n[3]; int ncell; };
 
-#define SEG_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-__device__ __forceinline__ void seg_publish(float* p, float v) { __hip_atomic_store(p, v, SEG_RLX); }
-__device__ __forceinline__ float seg_read(const float* p) { return __hip_atomic_load(p, SEG_RLX); }
-// every thread of the workgroup, after its seg_publish calls: true in the workgroup that arrives last
-__device__ __forceinline__ bool seg_arrive(int* ticket) {
-    __shared__ bool last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) last = __hip_atomic_fetch_add(ticket, 1, SEG_RLX) == (int)gridDim.x - 1;
-    __syncthreads();
-    return last;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ int seg_axis_cell(float x, float lo, float inv, int n) {
     const float c = floorf((x - lo) * inv);
     return (int)fminf(fmaxf(c, 0.f), (float)(n - 1));      // (fmaxf drops a NaN: such a point sorts into cell 0 and has no neighbours)
@@ -78,13 +57,13 @@ __global__ __launch_bounds__(256) void k_seg_bounds(int N, const float* __restri
         const int c = threadIdx.x;
         float v = red[0][c];
         for (int w = 1; w < 4; ++w) v = c < 3 ? fminf(v, red[w][c]) : fmaxf(v, red[w][c]);
-        seg_publish(partial + blockIdx.x * 6 + c, v);
+        publish(partial + blockIdx.x * 6 + c, v);
     }
-    if (!seg_arrive(ticket)) return;
+    if (!last_arrival(ticket, (int)gridDim.x)) return;
     if (threadIdx.x < 6) {
         const int c = threadIdx.x;
-        float v = seg_read(partial + c);
-        for (int w = 1; w < (int)gridDim.x; ++w) { const float u = seg_read(partial + w * 6 + c); v = c < 3 ? fminf(v, u) : fmaxf(v, u); }
+        float v = read_published(partial + c);
+        for (int w = 1; w < (int)gridDim.x; ++w) { const float u = read_published(partial + w * 6 + c); v = c < 3 ? fminf(v, u) : fmaxf(v, u); }
         fin[c] = v;
     }
     __syncthreads();
@@ -241,13 +220,14 @@ struct SegArgs {
     float* part1; float* part2; float* part3; float* mu; int* tickets;
 };
 
-// NV values per thread summed over the workgroup and published as this workgroup's partials
+// NV values per thread summed over the workgroup and published as this workgroup's partials.  Not reduce.h's block_sum_ordered: the four wave
+// sums are added PAIRWISE in fp32 (k_seg_points' line below does the same) - the sequential order gives other bits
 template <int NV> __device__ __forceinline__ void seg_block_publish(float* acc, float* red /* [4][NV] */, float* partial) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int v = 0; v < NV; ++v) { const float s = wave_sum(acc[v]); if (lane == 0) red[wv * NV + v] = s; }
     __syncthreads();
-    for (int v = threadIdx.x; v < NV; v += 256) seg_publish(partial + (int64_t)blockIdx.x * NV + v, (red[v] + red[NV + v]) + (red[2 * NV + v] + red[3 * NV + v]));
+    for (int v = threadIdx.x; v < NV; v += 256) publish(partial + (int64_t)blockIdx.x * NV + v, (red[v] + red[NV + v]) + (red[2 * NV + v] + red[3 * NV + v]));
 }
 
 template <int KP>
@@ -271,10 +251,10 @@ __global__ __launch_bounds__(256) void k_seg_moments1(SegArgs a) {
         }
     }
     seg_block_publish<7 * KP>(acc, red, a.part1);
-    if (!seg_arrive(a.tickets)) return;
+    if (!last_arrival(a.tickets, (int)gridDim.x)) return;
     for (int v = threadIdx.x; v < 7 * KP; v += 256) {
         double s = 0.0;
-        for (int w = 0; w < (int)gridDim.x; ++w) s += (double)seg_read(a.part1 + (int64_t)w * 7 * KP + v);
+        for (int w = 0; w < (int)gridDim.x; ++w) s += (double)read_published(a.part1 + (int64_t)w * 7 * KP + v);
         fin[v] = s;
     }
     __syncthreads();
@@ -361,10 +341,10 @@ __global__ __launch_bounds__(256) void k_seg_moments2(SegArgs a) {
         }
     }
     seg_block_publish<9 * KP>(acc, red, a.part2);
-    if (!seg_arrive(a.tickets + 1)) return;
+    if (!last_arrival(a.tickets + 1, (int)gridDim.x)) return;
     for (int v = threadIdx.x; v < 9 * KP; v += 256) {
         double s = 0.0;
-        for (int w = 0; w < (int)gridDim.x; ++w) s += (double)seg_read(a.part2 + (int64_t)w * 9 * KP + v);
+        for (int w = 0; w < (int)gridDim.x; ++w) s += (double)read_published(a.part2 + (int64_t)w * 9 * KP + v);
         fin[v] = s;
     }
     __syncthreads();
@@ -482,14 +462,14 @@ __global__ __launch_bounds__(256) void k_seg_points(SegArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { const float s = wave_sum(acc[c]); if (lane == 0) red[wv * 3 + c] = s; }
     __syncthreads();
-    if (threadIdx.x < 3) seg_publish(a.part3 + (int64_t)blockIdx.x * 3 + threadIdx.x, (red[threadIdx.x] + red[3 + threadIdx.x]) + (red[6 + threadIdx.x] + red[9 + threadIdx.x]));
-    if (!seg_arrive(a.tickets + 2)) return;
+    if (threadIdx.x < 3) publish(a.part3 + (int64_t)blockIdx.x * 3 + threadIdx.x, (red[threadIdx.x] + red[3 + threadIdx.x]) + (red[6 + threadIdx.x] + red[9 + threadIdx.x]));
+    if (!last_arrival(a.tickets + 2, (int)gridDim.x)) return;
     if (wv == 0) {
         float total = 0.f;
         for (int c = 0; c < 3; ++c) {
             double s = 0.0;
-            for (int w = lane; w < (int)gridDim.x; w += 64) s += (double)seg_read(a.part3 + (int64_t)w * 3 + c);
-            s = wave_sum_f64(s);
+            for (int w = lane; w < (int)gridDim.x; w += 64) s += (double)read_published(a.part3 + (int64_t)w * 3 + c);
+            s = wave_sum(s);
             const double den = c == 1 ? (double)a.N * (double)a.k : (double)a.N;
             const float v = (c == 0 && !rigid) || (c == 1 && !smooth) ? 0.f : (float)(s / den);
             if (lane == 0) a.losses[c] = v;

@@ -279,6 +279,39 @@ def test_switch_table_matches_the_integration_guide_and_is_the_only_reader():
     assert not kept, kept
 
 
+def test_reduction_and_point_wave_idioms_have_one_home():
+    """The device idioms of the loss and metric units are defined once (text only): the fp64 wave butterfly in reduce.h (common.h keeps its
+    float one), the ticket arrival that drains with s_waitcnt vmcnt(0) in reduce.h, and prod6 / the odd LDS stride of basis_mat / the
+    other-five product of the wave-per-point family in pointwave.h (scatter_atomic.hip, the render backward's scatter, keeps its own)."""
+    csrc = os.path.join(ROOT, "nvfi_amd", "csrc")
+    code = {fn: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, fn), errors="ignore").read(), flags=re.S)
+            for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h"))}
+    assert "reduce.h" in code and "pointwave.h" in code
+    kinds = r"\b(?:double|float|int|unsigned|T)\b"
+
+    def summed_types(txt):      # type of every X in `for (int o = 32; o > 0; o >>= 1) X += __shfl_xor(X, o)`: its nearest declaration in front
+        out = []
+        for m in re.finditer(r"for\s*\(\s*int\s+o\s*=\s*32\s*;\s*o\s*>\s*0\s*;\s*o\s*>>=\s*1\s*\)\s*\{?\s*(\w+)(\[\w+\])?\s*\+=\s*__shfl_xor\(\s*\1", txt):
+            decl = re.findall(r"(%s)(?:(?!%s)[^;(){}])*?\b%s\b" % (kinds, kinds, m.group(1)), txt[:m.start()])
+            out.append(decl[-1] if decl else "?")
+        return out
+
+    types = {fn: summed_types(txt) for fn, txt in code.items()}
+    assert types["reduce.h"] == ["T"] and types["common.h"] == ["float"], (types["reduce.h"], types["common.h"])
+    elsewhere = {fn: t for fn, t in types.items() if fn not in ("common.h", "reduce.h") and any(k in ("double", "T", "?") for k in t)}
+    assert not elsewhere, f"a wave butterfly over a double outside reduce.h: {elsewhere}"
+    # a function that returns "I am the last workgroup" after draining its stores: reduce.h's last_arrival only; the loss and metric units
+    # have no drain and no ticket draw of their own
+    arrivals = {fn: re.findall(r"\bbool\s+(\w+)\s*\(\s*int\s*\*\s*ticket[^)]*\)\s*\{[^}]*s_waitcnt vmcnt\(0\)", txt) for fn, txt in code.items()}
+    assert {fn: a for fn, a in arrivals.items() if a} == {"reduce.h": ["last_arrival"]}, arrivals
+    for fn in ("segloss.hip", "metrics.hip", "charloss.hip", "depthloss.hip", "raydist.hip", "flowloss.hip", "lookup.hip"):
+        assert "s_waitcnt" not in code[fn] and "__hip_atomic_fetch_add" not in code[fn], fn
+    homes = {"pointwave.h", "scatter_atomic.hip"}
+    for what, pattern in (("prod6", r"\bfloat\s+prod6\s*\("), ("stride 49", r"\b49\b"), ("other-five product", r"L\[p\]\s*=\s*L\[p - 1\]\s*\*\s*val\[p - 1\]")):
+        found = {fn for fn, txt in code.items() if re.search(pattern, txt)}
+        assert "pointwave.h" in found and found <= homes, f"{what}: {sorted(found)}"
+
+
 def _plan_desc():
     """nvfi_field_desc with the sizes of golden field A and no pointers: the workspace plan reads sizes only"""
     from nvfi_amd import _lib
