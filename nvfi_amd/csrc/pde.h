@@ -1,4 +1,6 @@
-// pde.h - argument blocks and stash geometry of the PDE kernels (pde.hip)
+// pde.h - what the units of the PDE regulariser share (pde.hip: prefilter, residuals, host path; pde_jet.hip / pde_jet6.hip / pde_fuse.hip: the
+// Jacobian passes) with each other and with the warp launchers they call: stash geometry, argument blocks, the device-side sizing of a pass and
+// the bookkeeping writers.  The pieces only the three jet kernels share are in pde_jet.h.
 #pragma once
 #include "common.h"
 #include "vel.h"
@@ -56,11 +58,32 @@ struct PdeJetArgs {
     int x4;                    // k_pde_jet_fwd: layers 0..3 of z / zd_j in x4 stash blocks (engine.h: stash_st16_x4) - their only reader is then k_pde_fuse_bwd
 };
 
+// whole 128-point groups: the jet workgroups, the stash and the weight-gradient kernels cover the ragged rows of the last group too (zero seeds)
+template <class T> __host__ __device__ __forceinline__ constexpr T pde_group_ceil(T n) { return (n + WG_SAMPLES - 1) / WG_SAMPLES * WG_SAMPLES; }
 // kept points of this pass: the launch grids are sized for the worst case (every candidate kept) and workgroups beyond the
 // device-side count leave at once - the host never learns the count, so the call needs no synchronisation
-__device__ __forceinline__ int pde_pass_count_of(const PdeJetArgs& a) {
-    const int64_t c = (int64_t)(*a.kcount) - a.first;
-    return c <= 0 ? 0 : (c > a.cap ? (int)a.cap : (int)c);
+// (first / cap by reference: the callers pass members of their argument block, and the loads stay where the block's own accessor had them -
+// k_pde_seeds and k_pde_fuse_bwd compile to the instructions they had with pde_pass_count_of / pf_count)
+__device__ __forceinline__ int pde_pass_count(const int* kcount, const int64_t& first, const int64_t& cap) {
+    const int64_t c = (int64_t)(*kcount) - first;
+    return c <= 0 ? 0 : (c > cap ? (int)cap : (int)c);
+}
+// The call's bookkeeping, written by ONE thread: the last workgroup of k_pde_seeds (pde_tail) or the stand-alone kernels of NVFI_FUSED_LAUNCH=0.
+// per-pass sample count for k_wgrad (whole 128-point groups: the ragged rows of the last group are zero)
+__device__ __forceinline__ void pde_write_pass_count(int* dcount, int count) {
+    *dcount = pde_group_ceil(count);
+    dcount[8] = 0;          // k_pde_fuse_bwd's queue of acceleration-net tiles
+}
+__device__ __forceinline__ void pde_write_finish(float* out, int64_t nk, double sd, double st) {
+    out[0] = nk > 0 ? (float)(5.0 * sd / (double)nk + 0.1 * st / (3.0 * (double)nk)) : 0.f;
+    out[1] = (float)nk; out[2] = (float)sd; out[3] = (float)st;
+}
+// counters[1] = candidates, [3] = prefilter net evaluations (2 per RK2 step, from the step-class histogram), [4] = kept points
+// [5] = points re-evaluated in fp32 behind the opt-in fp16 pre-pass (pre16.hip), 0 otherwise
+__device__ __forceinline__ void pde_write_counters(int64_t* c8, const int* cls_count, const int* kcount, int64_t P, int pre16) {
+    int64_t evals = 0;
+    for (int c = 0; c < PDE_MAX_CLASS; ++c) evals += 2ll * c * cls_count[c];
+    c8[0] = 0; c8[1] = P; c8[2] = 0; c8[3] = evals; c8[4] = *kcount; c8[5] = pre16 ? kcount[1] : 0; c8[6] = c8[7] = 0;
 }
 int launch_frag_x4(const X4Jobs& jobs, hipStream_t st);
 

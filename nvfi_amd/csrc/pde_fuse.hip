@@ -61,10 +61,6 @@ struct PfT { };
 #define PT_MFMA_DONE(acc) do { } while (0)
 #endif
 
-__device__ __forceinline__ int pf_count(const PdeFuseArgs& a) {
-    const int64_t c = (int64_t)(*a.kcount) - a.first;
-    return c <= 0 ? 0 : (c > a.cap ? (int)a.cap : (int)c);
-}
 // opaque_u (fuse.h) as a VOLATILE asm: the row-block bases of a tile are formed where they are used - left to loop-invariant code motion, the
 // tile-independent halves of ~60 of them are hoisted out of the persistent loop, overflow the SGPR file and come back as v_readlane / scratch reloads
 __device__ __forceinline__ gcfp pf_base(const float* p) { gcfp q = (gcfp)p; asm volatile("" : "+s"(q)); return q; }
@@ -604,9 +600,9 @@ __global__ __launch_bounds__(PF_THREADS) void k_pde_fuse_bwd(PdeFuseArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int count = __builtin_amdgcn_readfirstlane(pf_count(a));
+    const int count = __builtin_amdgcn_readfirstlane(pde_pass_count(a.kcount, a.first, a.cap));
     // whole 128-point groups, as the forward stashed them
-    const int ntiles = (count + WG_SAMPLES - 1) / WG_SAMPLES * (WG_SAMPLES / TILE);
+    const int ntiles = pde_group_ceil(count) / TILE;
     if (wave < 4) {
         __builtin_amdgcn_s_setprio(3);
         pf_role_adjoint(a, reinterpret_cast<float4*>(lds), wave, lane, ntiles);

@@ -21,10 +21,11 @@
 // velnet_value_backward of pde.h in the adjoint); pde_jet6.hip is this forward with the hidden layers on the 16-bit matrix pipe, and
 // pde_fuse.hip the adjoint fused with the hidden layers' weight gradients.  k_frag_x4 below makes the x4 weight copies of an uncached
 // call from its plain fragments (the jobs are vel_images', frags.hip).
+// What this unit shares with pde_jet6.hip - the MFMA loop, the encoder tangents, the output stage, the trailing workgroups - is in pde_jet.h.
 #include <stdio.h>
 #include <stdlib.h>
 #include "common.h"
-#include "pde.h"
+#include "pde_jet.h"
 
 // ---------------------------------------------------------------- x4 fragments: four consecutive K steps of a lane side by side
 // dst[((m*NS4 + s4)*64 + lane)*4 + k] = src[(m*NS + 4*s4 + k)*64 + lane]  (zero beyond NS)
@@ -47,27 +48,8 @@ int launch_frag_x4(const X4Jobs& jobs, hipStream_t st) {
     return 0;
 }
 
-#define JET_NC 5
 #define JET_XCH_FLOATS (JET_NC * 64 * 64)        // 80 KB: [column][s/4][lane][4]
 #define JET_LDS_BYTES (JET_XCH_FLOATS * 4)
-
-// acc[c] += sum over NS4 groups of 4 K-steps:  A = this wave's x4 fragment (one 16-byte load per group, next group in flight),
-// B = x[c][s_base + ...] for the five columns
-template <int NS4, int XS>
-__device__ __forceinline__ void jet_mfma(const float4* __restrict__ a4, int lane, const float (&x)[JET_NC][XS], int s_base, f32x16* acc) {
-    float4 cur = a4[lane];
-#pragma unroll
-    for (int g = 0; g < NS4; ++g) {
-        float4 nxt = cur;
-        if (g + 1 < NS4) nxt = a4[(g + 1) * 64 + lane];
-        const float av[4] = {cur.x, cur.y, cur.z, cur.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < JET_NC; ++c) acc[c] = MFMA32(av[k], x[c][s_base + 4 * g + k], acc[c]);
-        cur = nxt;
-    }
-}
 
 // every wave publishes its 16 registers per column, then reads the whole 64-register layer input of all five columns
 __device__ __forceinline__ void jet_exchange(float4* xch, int w, int lane, const f32x16* out, float (&x)[JET_NC][64]) {
@@ -87,54 +69,20 @@ __device__ __forceinline__ void jet_exchange(float4* xch, int w, int lane, const
         }
 }
 
-// tangent of the PositionEncoder slots wrt q_j (same as pde.hip: encode_tangent)
-__device__ __forceinline__ void jet_encode_tangent(const float* x0, int h, int j, float* xd) {
-#pragma unroll
-    for (int s = 0; s < 16; ++s) xd[s] = 0.f;
-    if (j == 0 && h == 0) xd[0] = 1.f;
-    if (j == 1 && h == 1) xd[0] = 1.f;
-    if (j == 2 && h == 0) xd[1] = 1.f;
-    if (j == 3 && h == 1) xd[1] = 1.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float mine = x0[2 + 4 * k + c];
-            const float other = __shfl_xor(mine, 32);
-            const float fr = (float)(1 << k);
-            if (c == j) xd[2 + 4 * k + c] = h ? -fr * other : fr * other;
-        }
-}
-
 // ---------------------------------------------------------------- forward: value + 4 tangents of weight_net
 __global__ __launch_bounds__(WG_THREADS, 2) void k_pde_jet_fwd(PdeJetArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float4* xch = reinterpret_cast<float4*>(lds);
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int count = pde_pass_count_of(a);
+    const int count = pde_pass_count(a.kcount, a.first, a.cap);
     if ((int)blockIdx.x >= a.jet_tiles) {
-        // trailing workgroups: value column of the ReLU acceleration net for 4 tiles (the column kernel of pde.hip, riding in this
-        // launch so that its one round of workgroups fills the tail of the jet tiles instead of a launch of its own)
-        const int wg = blockIdx.x - a.jet_tiles;
-        if (wg * WG_SAMPLES >= count) return;
-        const int tile = wg * 4 + w;
-        const int i = tile * TILE + (lane & 31);
-        const float4 q = i < count ? a.qorig[a.klist[a.first + i]] : zero4();
-        float* T = a.stash + (size_t)tile * PDE_TILE_ROWS * REGF;
-        float o4[4], aw[6];
-        velnet_forward<0, true>(a.Wa, lds, lds + LDS_W_FLOATS, lane, q, T + PDE_ZA * REGF, nullptr, o4);
-        gather6(o4, h, aw);
-        if (h == 0 && i < a.cap) {
-            float* o = a.wout + (size_t)30 * a.cap + i;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) o[(size_t)k * a.cap] = aw[k];
-        }
+        jet_anet_forward(a, lds, count, w, lane, h);
         return;
     }
     const int tile = blockIdx.x;
     // whole 128-point groups: the weight-gradient kernel walks the tiles of the last, ragged group too (zero seeds, finite z)
-    if (tile * TILE >= (count + WG_SAMPLES - 1) / WG_SAMPLES * WG_SAMPLES) return;
+    if (tile * TILE >= pde_group_ceil(count)) return;
     const int i = tile * TILE + (lane & 31);
     const bool active = i < count;
     const float4 q = active ? a.qorig[a.klist[a.first + i]] : zero4();
@@ -193,46 +141,13 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_pde_jet_fwd(PdeJetArgs a) {
         }
         jet_mfma<16, 64>(a.f4[l + 1] + (size_t)w * 16 * 64, lane, x, 0, acc);
     }
-    // output layer 128 -> 6, split along K: this wave contracts its own 32 rows (registers of acc), partial sums meet in LDS
-    {
-        float o[JET_NC][16];
+    // output layer 128 -> 6 (pde_jet.h)
+    float o[JET_NC][16];
 #pragma unroll
-        for (int c = 0; c < JET_NC; ++c)
+    for (int c = 0; c < JET_NC; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[c][r] = acc[c][r];
-#pragma unroll
-        for (int c = 0; c < JET_NC; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-        jet_mfma<4, 16>(a.f4[5] + (size_t)(4 * w) * 64, lane, o, 0, acc);
-        __syncthreads();      // the exchange buffer's last readers are done
-        float* red = lds;     // [wave][column][4 regs][64 lanes]
-#pragma unroll
-        for (int c = 0; c < JET_NC; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[((w * JET_NC + c) * 4 + r) * 64 + lane] = acc[c][r];
-        __syncthreads();
-        if (w == 0 && h == 0 && i < a.cap) {
-#pragma unroll
-            for (int c = 0; c < JET_NC; ++c) {
-                float o6[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    // output k lives in register k&3 of half k>>2 (D layout rows 0..3 | 4..7): lanes l (h=0) and l+32 (h=1)
-                    const int ln = lane + 32 * (k >> 2), r = k & 3;
-                    float s = c == 0 ? a.bv[5][k] : 0.f;
-                    s = s + red[((0 * JET_NC + c) * 4 + r) * 64 + ln];
-                    s = s + red[((1 * JET_NC + c) * 4 + r) * 64 + ln];
-                    s = s + red[((2 * JET_NC + c) * 4 + r) * 64 + ln];
-                    s = s + red[((3 * JET_NC + c) * 4 + r) * 64 + ln];
-                    o6[k] = s;
-                }
-                float* o = a.wout + (size_t)(c == 0 ? 0 : 6 * c) * a.cap + i;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) o[(size_t)k * a.cap] = o6[k];
-            }
-        }
-    }
+        for (int r = 0; r < 16; ++r) o[c][r] = acc[c][r];
+    jet_output_stage(a, lds, o, w, lane, h, i);
 }
 
 // ---------------------------------------------------------------- backward: 4 tangent adjoints + value adjoint with the corrections
@@ -241,23 +156,13 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_pde_jet_bwd(PdeJetArgs a) {
     float4* xch = reinterpret_cast<float4*>(lds);
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int count = pde_pass_count_of(a);
+    const int count = pde_pass_count(a.kcount, a.first, a.cap);
     if ((int)blockIdx.x >= a.jet_tiles) {
-        // trailing workgroups: adjoint of the acceleration net's value column (4 tiles per workgroup)
-        const int wg = blockIdx.x - a.jet_tiles;
-        if (wg * WG_SAMPLES >= count) return;
-        const int tile = wg * 4 + w;
-        const int i = tile * TILE + (lane & 31);
-        float* T = a.stash + (size_t)tile * PDE_TILE_ROWS * REGF;
-        float r4[4], s6[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s6[k] = i < (int)a.cap ? a.seeds[(size_t)(30 + k) * a.cap + i] : 0.f;
-        scatter6(s6, h, r4);
-        velnet_value_backward<0>(a.Wa, lds, lds + LDS_W_FLOATS, lane, r4, T + PDE_ZA * REGF, T + PDE_GAA * REGF);
+        jet_anet_backward(a, lds, count, w, lane, h);
         return;
     }
     const int tile = blockIdx.x;
-    if (tile * TILE >= (count + WG_SAMPLES - 1) / WG_SAMPLES * WG_SAMPLES) return;
+    if (tile * TILE >= pde_group_ceil(count)) return;
     const int i = tile * TILE + (lane & 31);
     float* T = a.stash + (size_t)tile * PDE_TILE_ROWS * REGF;
     const size_t cs = a.cap;

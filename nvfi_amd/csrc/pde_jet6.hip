@@ -11,19 +11,18 @@
 // and wave: 240 MFMAs of 32 cycles instead of 320 of 64.  The epilogue is k_pde_jet_fwd's - the pre-activations z / zd_j go to the SAME
 // stash rows in the same layout (x4 blocks for layers 0..3), SiLU and SiLU' once per row for the five columns - plus the split of the 5 x 16
 // outputs; the 128 -> 6 output layer stays on the fp32 MFMA (K split over the waves, partial sums through LDS) and the acceleration net's
-// value column rides in the launch's trailing workgroups, both exactly as in pde_jet.hip.
+// value column rides in the launch's trailing workgroups: both are pde_jet.hip's, shared through pde_jet.h.
 // Numerics: z / zd_j differ from the fp32 kernel's by the rounding of another summation order (exact products, fp32 accumulation): the PDE
 // goldens (kept set, Jacobian rows, loss, gradients) pass unchanged; NVFI_PDE_JET_X6=0 keeps k_pde_jet_fwd.
 #include <stdlib.h>
 #include <stdio.h>
 #include "common.h"
 #include "vel.h"
-#include "pde.h"
+#include "pde_jet.h"
 #include "engine16.h"
 #include "x6.h"
 
-#define J6_NC 5
-#define J6_XCH_H8 (J6_NC * 8 * 3 * 64)                 // [column][K step][term][lane] 16-byte operands
+#define J6_XCH_H8 (JET_NC * 8 * 3 * 64)                 // [column][K step][term][lane] 16-byte operands
 #define J6_LDS_BYTES (J6_XCH_H8 * 16)
 static_assert(J6_LDS_BYTES >= ENGINE_LDS_BYTES, "the trailing acceleration-net workgroups stage their fragments in the same LDS");
 // -DJ6_TIMING: wave 0 of workgroup 0 accumulates shader-clock intervals: [0] layer 0, [1] epilogue (stash, SiLU), [2] barrier 1, [3] split + LDS writes,
@@ -37,66 +36,18 @@ __device__ unsigned long long j6_times[8];
 typedef const b8_t __attribute__((address_space(1)))* j6_gptr;
 __device__ __forceinline__ j6_gptr j6_base(const b8_t* p) { j6_gptr q = (j6_gptr)p; asm("" : "+s"(q)); return q; }
 
-// tangent of the PositionEncoder slots wrt q_j (pde_jet.hip: jet_encode_tangent)
-__device__ __forceinline__ void j6_encode_tangent(const float* x0, int h, int j, float* xd) {
-#pragma unroll
-    for (int s = 0; s < 16; ++s) xd[s] = 0.f;
-    if (j == 0 && h == 0) xd[0] = 1.f;
-    if (j == 1 && h == 1) xd[0] = 1.f;
-    if (j == 2 && h == 0) xd[1] = 1.f;
-    if (j == 3 && h == 1) xd[1] = 1.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float mine = x0[2 + 4 * k + c];
-            const float other = __shfl_xor(mine, 32);
-            const float fr = (float)(1 << k);
-            if (c == j) xd[2 + 4 * k + c] = h ? -fr * other : fr * other;
-        }
-}
-// the fp32 output layer of pde_jet.hip (jet_mfma<4, 16>): acc[c] += A (x4 fragment, four K steps per 16-byte load) x x[c]
-__device__ __forceinline__ void j6_out_mfma(const float4* __restrict__ a4, int lane, const float (&x)[J6_NC][16], f32x16* acc) {
-    float4 cur = a4[lane];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        float4 nxt = cur;
-        if (g + 1 < 4) nxt = a4[(g + 1) * 64 + lane];
-        const float av[4] = {cur.x, cur.y, cur.z, cur.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < J6_NC; ++c) acc[c] = MFMA32(av[k], x[c][4 * g + k], acc[c]);
-        cur = nxt;
-    }
-}
-
 __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, const b8_t* __restrict__ img) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     b8_t* xch = reinterpret_cast<b8_t*>(lds);
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int count = pde_pass_count_of(a);
+    const int count = pde_pass_count(a.kcount, a.first, a.cap);
     if ((int)blockIdx.x >= a.jet_tiles) {
-        // trailing workgroups: value column of the ReLU acceleration net for 4 tiles (pde_jet.hip)
-        const int wg = blockIdx.x - a.jet_tiles;
-        if (wg * WG_SAMPLES >= count) return;
-        const int tile = wg * 4 + w;
-        const int i = tile * TILE + (lane & 31);
-        const float4 q = i < count ? a.qorig[a.klist[a.first + i]] : zero4();
-        float* T = a.stash + (size_t)tile * PDE_TILE_ROWS * REGF;
-        float o4[4], aw[6];
-        velnet_forward<0, true>(a.Wa, lds, lds + LDS_W_FLOATS, lane, q, T + PDE_ZA * REGF, nullptr, o4);
-        gather6(o4, h, aw);
-        if (h == 0 && i < a.cap) {
-            float* o = a.wout + (size_t)30 * a.cap + i;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) o[(size_t)k * a.cap] = aw[k];
-        }
+        jet_anet_forward(a, lds, count, w, lane, h);
         return;
     }
     const int tile = blockIdx.x;
-    if (tile * TILE >= (count + WG_SAMPLES - 1) / WG_SAMPLES * WG_SAMPLES) return;
+    if (tile * TILE >= pde_group_ceil(count)) return;
     const int i = tile * TILE + (lane & 31);
     const bool active = i < count;
     const float4 q = active ? a.qorig[a.klist[a.first + i]] : zero4();
@@ -106,7 +57,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
     const bool tm = blockIdx.x == 0 && threadIdx.x == 0;
     unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = __builtin_amdgcn_s_memtime();
 #endif
-    f32x16 a0[J6_NC], a1[J6_NC];
+    f32x16 a0[JET_NC], a1[JET_NC];
     // ---- layer 0 (28 -> 128): every wave encodes the point and its four encoder tangents itself; 2 K steps
     {
         b8_t A1[2], A2[2], A3[2];
@@ -123,16 +74,16 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
             a0[0][r] = a.bv[0][32 * w + (r & 3) + 8 * (r >> 2) + 4 * h];
             a1[0][r] = 0.f;
 #pragma unroll
-            for (int c = 1; c < J6_NC; ++c) { a0[c][r] = 0.f; a1[c][r] = 0.f; }
+            for (int c = 1; c < JET_NC; ++c) { a0[c][r] = 0.f; a1[c][r] = 0.f; }
         }
 #pragma unroll
-        for (int c = 0; c < J6_NC; ++c) {
+        for (int c = 0; c < JET_NC; ++c) {
             float xin[16];
             if (c == 0) {
 #pragma unroll
                 for (int s = 0; s < 16; ++s) xin[s] = x0[s];
             } else {
-                j6_encode_tangent(x0, h, c - 1, xin);
+                jet_encode_tangent(x0, h, c - 1, xin);
                 if (w == c - 1) stash_store<16>(T + (PDE_X0D + 16 * (c - 1)) * REGF, lane, xin);
             }
 #pragma unroll
@@ -143,7 +94,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
             }
         }
     }
-    float act[J6_NC][16];
+    float act[JET_NC][16];
 #ifdef J6_TIMING
     asm volatile("s_nop 0" :: "v"(a1[4][0]));
 #endif
@@ -161,9 +112,9 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
         const int row0 = l * 64 + 16 * w;
         const bool x4 = a.x4 && l < 4;
         {
-            f32x16 zc[J6_NC];
+            f32x16 zc[JET_NC];
 #pragma unroll
-            for (int c = 0; c < J6_NC; ++c)
+            for (int c = 0; c < JET_NC; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) zc[c][r] = a1[c][r] + a0[c][r];
             if (x4) {
@@ -191,7 +142,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
         __syncthreads();                                 // the previous layer's readers of the exchange images are done
         J6_T(2);
 #pragma unroll
-        for (int c = 0; c < J6_NC; ++c)
+        for (int c = 0; c < JET_NC; ++c)
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 b8_t b1, b2, b3;
@@ -204,7 +155,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
             a0[0][r] = a.bv[l + 1][32 * w + (r & 3) + 8 * (r >> 2) + 4 * h];
             a1[0][r] = 0.f;
 #pragma unroll
-            for (int c = 1; c < J6_NC; ++c) { a0[c][r] = 0.f; a1[c][r] = 0.f; }
+            for (int c = 1; c < JET_NC; ++c) { a0[c][r] = 0.f; a1[c][r] = 0.f; }
         }
         J6_T(3);
         __syncthreads();
@@ -215,15 +166,15 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
             b8_t Bq[2][3];
             { const b8_t* src = xch + lane; Bq[0][0] = src[0]; Bq[0][1] = src[64]; Bq[0][2] = src[128]; }
 #pragma unroll
-            for (int it = 0; it < 8 * J6_NC; ++it) {
-                const int s = it / J6_NC, c = it % J6_NC;
-                if (it + 1 < 8 * J6_NC) {
-                    const int s2 = (it + 1) / J6_NC, c2 = (it + 1) % J6_NC;
+            for (int it = 0; it < 8 * JET_NC; ++it) {
+                const int s = it / JET_NC, c = it % JET_NC;
+                if (it + 1 < 8 * JET_NC) {
+                    const int s2 = (it + 1) / JET_NC, c2 = (it + 1) % JET_NC;
                     const b8_t* src = xch + (size_t)((c2 * 8 + s2) * 3) * 64 + lane;
                     Bq[(it + 1) & 1][0] = src[0]; Bq[(it + 1) & 1][1] = src[64]; Bq[(it + 1) & 1][2] = src[128];
                 }
                 x6_mm6(A1[s & 1], A2[s & 1], A3[s & 1], Bq[it & 1][0], Bq[it & 1][1], Bq[it & 1][2], a0[c], a1[c]);
-                if (c == J6_NC - 1 && s + 2 < 8) { A1[s & 1] = P1[(s + 2) * 64 + lane]; A2[s & 1] = P2[(s + 2) * 64 + lane]; A3[s & 1] = P3[(s + 2) * 64 + lane]; }
+                if (c == JET_NC - 1 && s + 2 < 8) { A1[s & 1] = P1[(s + 2) * 64 + lane]; A2[s & 1] = P2[(s + 2) * 64 + lane]; A3[s & 1] = P3[(s + 2) * 64 + lane]; }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -232,41 +183,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void k_pde_jet6_fwd(PdeJetArgs a, co
 #endif
         J6_T(5);
     }
-    // ---- output layer 128 -> 6 on the fp32 MFMA, split along K: this wave contracts its own 32 rows, partial sums meet in LDS (pde_jet.hip)
-    {
-        f32x16 acc[J6_NC];
-#pragma unroll
-        for (int c = 0; c < J6_NC; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-        j6_out_mfma(a.f4[5] + (size_t)(4 * w) * 64, lane, act, acc);
-        __syncthreads();      // the exchange images' last readers are done
-        float* red = lds;     // [wave][column][4 regs][64 lanes]
-#pragma unroll
-        for (int c = 0; c < J6_NC; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[((w * J6_NC + c) * 4 + r) * 64 + lane] = acc[c][r];
-        __syncthreads();
-        if (w == 0 && h == 0 && i < a.cap) {
-#pragma unroll
-            for (int c = 0; c < J6_NC; ++c) {
-                float o6[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int ln = lane + 32 * (k >> 2), r = k & 3;
-                    float s = c == 0 ? a.bv[5][k] : 0.f;
-                    s = s + red[((0 * J6_NC + c) * 4 + r) * 64 + ln];
-                    s = s + red[((1 * J6_NC + c) * 4 + r) * 64 + ln];
-                    s = s + red[((2 * J6_NC + c) * 4 + r) * 64 + ln];
-                    s = s + red[((3 * J6_NC + c) * 4 + r) * 64 + ln];
-                    o6[k] = s;
-                }
-                float* o = a.wout + (size_t)(c == 0 ? 0 : 6 * c) * a.cap + i;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) o[(size_t)k * a.cap] = o6[k];
-            }
-        }
-    }
+    // ---- output layer 128 -> 6 on the fp32 MFMA (pde_jet.h)
+    jet_output_stage(a, lds, act, w, lane, h, i);
     J6_T(6);
 #ifdef J6_TIMING
     if (tm) { for (int k = 0; k < 7; ++k) j6_times[k] = tacc[k]; j6_times[7] = 1; }

@@ -1,4 +1,4 @@
-// pre16.hip - OPT-IN fp16-input pre-pass of the PDE occupancy prefilter (NVFI_PDE_PREFILTER=fp16band; fp32 stays the default).
+// pre16.hip - OPT-IN fp16-input pre-pass of the PDE occupancy prefilter (NVFI_PDE_PREFILTER=fp16band; x6 is the default).
 //
 // The prefilter (reference models/nvfi.py:50-64) only DECIDES which collocation points take part in the PDE loss: RK2
 // back-advection (models/tensorf_keyframe.py:575-611), density at the warped point, alpha >= alphaMask_thres.  The decision is

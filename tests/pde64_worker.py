@@ -1,6 +1,6 @@
 """helper of tests/test_gpu_pde64.py (subprocess: the NVFI_* switches are read once per process): runs get_vel_loss on the device for the cases
-named on the command line and saves, per case, the inputs, the kept mask, the first 64 Jacobians, the loss, the kept count and the 24 gradients,
-plus the 24 parameters of every model used.   python tests/pde64_worker.py OUT.npz CASE[,CASE...]
+named on the command line and saves, per case, the inputs, the kept mask, the first 64 Jacobians, the loss, the kept count, the 24 gradients, the
+call's bookkeeping (out[0..3]: loss, kept count, sum div^2, sum transport^2; the eight counters), plus the 24 parameters of every model used.   python tests/pde64_worker.py OUT.npz CASE[,CASE...]
 
 Cases: `head` (the bench field, 262 144 points, a moving velocity field), `B<P>` (field B, which keeps every point of its box: P points),
 `bigz` (field B with the first layer of both nets scaled by 2.5 and the four hidden ones by 4: pre-activations up to 25-35, 32 768 points), `abi<P>` (field B, P points,
@@ -83,6 +83,7 @@ def run_case(name, out):
     out[f"{name}:points"], out[f"{name}:t"], out[f"{name}:kept"], out[f"{name}:jac"] = pts, tt[:, 0], kept, jac
     out[f"{name}:loss"], out[f"{name}:n_kept"] = np.float64(lv.detach().cpu()), np.int64(n)
     out[f"{name}:split"] = np.array(bool(f.pde_split) and P <= 262144)      # a split call (nvfi_pde_loss_split with a side stream, one chunk)
+    out[f"{name}:out"], out[f"{name}:counters"] = f.last_pde_out.cpu().numpy(), f.last_pde_counters.cpu().numpy()
     for i, p in enumerate(f._pde_params()):
         out[f"{name}:g{i}"] = p.grad.detach().cpu().numpy()
     save_model(kind, out)
@@ -118,6 +119,7 @@ def run_abi(name, P, out):
         out[f"{key}:model"] = np.array("B")
         out[f"{key}:points"], out[f"{key}:t"], out[f"{key}:kept"] = pts, tt[:, 0], kept.cpu().numpy().astype(bool)
         out[f"{key}:loss"], out[f"{key}:n_kept"] = np.float64(o[0].cpu()), np.int64(round(float(o[1])))
+        out[f"{key}:out"], out[f"{key}:counters"] = o.cpu().numpy(), cnt.cpu().numpy()
         for i, g in enumerate(grads):
             out[f"{key}:g{i}"] = g.cpu().numpy()
         print(key, "kept", int(out[f"{key}:n_kept"]), "of", P, flush=True)

@@ -4,7 +4,7 @@ against its float64 restatement (tests/pde64.py, pinned to the reference's golde
 Cases (tests/pde64_worker.py): the headline shape (the bench field, P = 262 144, a moving velocity field); field B, which keeps every point, at
 kept counts that sit on the kernel's edges - partial tiles and 128-point workgroups (1, 31, 33, 127, 129), the workgroup grants of k_pde_fuse_bwd,
 and one 262 144-point chunk exactly, a second chunk holding one point, two and three chunks; and large pre-activations.
-The grant depends on the call (pde.hip, nvfi_pde_loss_ex): a split call - get_vel_loss with the default NVFI_PDE_SPLIT=1 and P <= 262 144 -
+The grant depends on the call (pde.hip, pde_fused_adjoint): a split call - get_vel_loss with the default NVFI_PDE_SPLIT=1 and P <= 262 144 -
 grants PDE_NSLAB - 8 = 248 workgroups; NVFI_PDE_SPLIT=0, the multi-chunk calls and nvfi_pde_loss_ex without a second stream grant 256.  So
 under the defaults 32 x 248 and 32 x 248 + 1 points fill the 248 grant exactly and go one tile over it (32 x 256 + 5 is nine tiles over it), and
 the one_stream setting runs 32 x 256 and 32 x 256 + 5 points: the 256 grant filled exactly and one partial tile over it.  The worker records
@@ -26,8 +26,9 @@ Measured on one MI355X (defaults; the switches agree to within 2x): worst gradie
 acceleration net's hidden layers: fp32 slab sums and the occasional ReLU unit within rounding of its kink); on the 256 grant (one_stream)
 1.6e-7 at 32 x 256 and 32 x 256 + 5 points; loss <= 3e-7, Jacobian <= 3.3e-6.
 The one-tile shift at 528 421 kept points is 5.1e-5, so B = 1.5e-5 (the issue's starting value 2e-5 could not see a dropped tile there).
-The file takes about 35 s (seven worker processes).  A mutation of pf_count (pde_fuse.hip) that drops the last kept point of a pass whenever
-more than 32 are left fails the 129-point, 249-tile and partial-gradient cases here; every older PDE test passed on it."""
+The file takes about 35 s (seven worker processes).  A mutation of pde_pass_count (pde.h; then pf_count of pde_fuse.hip) that drops the last
+kept point of a pass whenever more than 32 are left fails the 129-point, 249-tile and partial-gradient cases here; every older PDE test passed
+on it.  The unfused_launch setting also pins the call's bookkeeping (out[1..3], the counters: pde.h's writers) to the defaults' values."""
 import hashlib
 import os
 import subprocess
@@ -171,6 +172,24 @@ def test_two_chunk_cases_do_reach_the_later_chunks():
     assert int(z["B262145:n_kept"]) == 262145 and int(z["B528421:n_kept"]) > 2 * 262144 and int(z["B266277:n_kept"]) > 262144
 
 
+def _bookkeeping_matches_the_fused_launch(z, zd):
+    """out[] and the counters are written by pde.h's writers from two callers: the last workgroup of k_pde_seeds (defaults) and the stand-alone
+    k_pde_pass_count / k_pde_finish / k_pde_counters launches (NVFI_FUSED_LAUNCH=0).  On the cases both workers run, the integers (the eight
+    counters, the kept count in out[1]) are equal exactly; out[2], out[3] (sum div^2, sum transport^2) are accumulated with atomics in an
+    order that differs from run to run and agree within the loss bound.  B266277 is the two-chunk case: the ticket is drawn from zero again
+    in the second pass, or out[] is never written."""
+    for case in SWITCH_CASES:
+        cu, cf = z[f"{case}:counters"], zd[f"{case}:counters"]
+        ou, of = z[f"{case}:out"].astype(np.float64), zd[f"{case}:out"].astype(np.float64)
+        rel = np.abs(ou[2:4] - of[2:4]) / np.abs(of[2:4])
+        print(f"[pde64] unfused_launch vs defaults, {case}: counters {cu.tolist()} / {cf.tolist()}, out[1] {ou[1]:.0f} / {of[1]:.0f}, "
+              f"sums rel diff {rel[0]:.2e}, {rel[1]:.2e}")
+        assert cu.shape == (8,) and cu.dtype == np.int64 and np.array_equal(cu, cf), (case, cu, cf)
+        assert int(cu[1]) == z[f"{case}:points"].shape[0] and int(cu[4]) == int(z[f"{case}:n_kept"]), (case, cu)
+        assert ou[1] == of[1] == float(z[f"{case}:n_kept"]), (case, ou[1], of[1])
+        assert (rel <= 1e-5).all(), (case, "sum div^2 / sum transport^2", rel)
+
+
 @pytest.mark.parametrize("setting", list(SWITCHES))
 def test_pde_switch_matches_float64(setting):
     cases = SWITCH_CASES + EXTRA_CASES.get(setting, [])
@@ -182,6 +201,8 @@ def test_pde_switch_matches_float64(setting):
         except AssertionError as e:
             bad.append(f"{case}: {e}")
     assert not bad, bad
+    if setting == "unfused_launch":
+        _bookkeeping_matches_the_fused_launch(z, _defaults())
 
 
 @pytest.mark.parametrize("drop", ["accel", "layer2"])
