@@ -470,6 +470,34 @@ int nvfi_appfeat_grad(const nvfi_field_desc* f, int64_t N, const float* xyzt, co
  * nvfi_render_bwd).  Errors (2), before anything is launched: an unsupported descriptor, N >= 2^31 - 256 (chunk the points). */
 int nvfi_render_mlp(const nvfi_field_desc* f, int64_t N, const float* xyz, const float* view, const float* features, float* rgb,
                     void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- differentiable point shading (an addition to ABI v5; csrc/point_shade.hip): the adjoint of rgb = nvfi_render_mlp(xyz, view, features) as
+ *      autograd carries it through the reference's plain torch code - MLPRender_PE.forward (tensorf_base.py:88-98: positional encodings of
+ *      pts and viewdirs, three Linear layers, ReLU, sigmoid) or, with shading = 1, SHRender (tensorf_model_utils.py:292-296 + sh.py:
+ *      relu(sum_k SH_k(view) feat[9c + k] + 0.5)).  Like nvfi_advect_grad the call keeps nothing from the forward: it runs k_app_fwd again in
+ *      stash form on the caller's features, then k_pshade_bwd (one 32-point tile per wave on the fp32 MFMA engine) and the render's split-K
+ *      weight-gradient jobs on that stash.
+ *        g_rgb       (N,3): the upstream gradient d loss / d rgb.  The seeds are g_rgb_c c (1 - c) with c the replayed sigmoid output (MLP_PE),
+ *                    resp. g_rgb_c where the replayed colour is > 0 (SH: torch's relu backward).
+ *        g_features  (N, app_dim), OVERWRITTEN (plain stores; may be NULL).
+ *        g_xyz       (N,3), OVERWRITTEN (may be NULL): the raw slot plus the chain through sin / cos (2^k x); zeros under SH, which does not read xyz.
+ *        g_view      (N,3), OVERWRITTEN (may be NULL): the same rule on the view slots; under SH through the derivatives of the nine bases.
+ *                    The three per-point outputs repeat bit for bit.
+ *        grads       rW[3] / rb[3]: ACCUMULATED (+=, one float atomic per entry and call, from slabs summed in a fixed order: a call into cleared
+ *                    buffers repeats bit for bit) into buffers the caller cleared; a NULL member (or grads == NULL) skips that tensor; no other
+ *                    member is read.  Ignored under SH (there is no MLP).
+ *      All launches go to `stream`, no host wait, nothing is cleared with a memset: the call can be captured in a hipGraph.  N == 0: nothing is
+ *      launched or written, 0 is returned.  Workspace (caller-allocated, may be reused by the next call on the same stream): 3 KB of stash and
+ *      32 B of packed points per point, 1 KB of ReLU masks per 32-point tile, the weight fragments (0.5 MB) and three slab sets (51 MB) - chunk
+ *      a large N; the weight gradients of the chunks accumulate.  Errors, before anything is launched: (2) an unsupported descriptor,
+ *      N >= 2^31 - 256, a NULL xyz / view / features / g_rgb; (4) a workspace under nvfi_render_mlp_grad_workspace_bytes(f, N). */
+int nvfi_render_mlp_grad_workspace_bytes(const nvfi_field_desc* f, int64_t N, int64_t* bytes);
+int nvfi_render_mlp_grad(const nvfi_field_desc* f, int64_t N,
+                         const float* xyz /* (N,3) */, const float* view /* (N,3) */, const float* features /* (N, app_dim) */,
+                         const float* g_rgb /* (N,3) */,
+                         float* g_features /* (N, app_dim) or NULL, OVERWRITTEN */,
+                         float* g_xyz /* (N,3) or NULL, OVERWRITTEN */, float* g_view /* (N,3) or NULL, OVERWRITTEN */,
+                         const nvfi_grads* grads /* rW[3] / rb[3] ACCUMULATED; NULL members (or grads == NULL) skipped; nothing else read */,
+                         void* workspace, int64_t workspace_bytes, void* stream);
 /* ---- multi-GPU: rays and collocation points shard over one process per GPU; the ONLY data-path exchange is the sum of the
  *      flat fp32 gradient buffer (the reference has no distributed code: models/ is single-device).  RCCL over xGMI,
  *      loaded lazily with dlopen.  Bootstrap: rank 0 gets a 128-byte id, the host program distributes it, every rank inits.

@@ -77,6 +77,7 @@ EXPORTS = [
     "nvfi_ray_distortion_workspace_bytes", "nvfi_ray_distortion",
     "nvfi_flow_loss_workspace_bytes", "nvfi_flow_loss_fwd", "nvfi_flow_loss_bwd",
     "nvfi_density_grad", "nvfi_appfeat_at", "nvfi_appfeat_grad",
+    "nvfi_render_mlp_grad_workspace_bytes", "nvfi_render_mlp_grad",
 ]
 
 _LIB = None
@@ -118,6 +119,8 @@ def lib():
         L.nvfi_density_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
         L.nvfi_appfeat_at.argtypes = [fp, C.c_int64, fp, fp, fp]
         L.nvfi_appfeat_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
+        L.nvfi_render_mlp_grad_workspace_bytes.argtypes = [fp, C.c_int64, i64p]
+        L.nvfi_render_mlp_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, fp]
         _LIB = L
     return _LIB
 

@@ -326,6 +326,53 @@ class _AdvectFn(torch.autograd.Function):
         return (None, gx, None, None, None) + tuple(grads)
 
 
+class _ShadeFn(torch.autograd.Function):
+    """autograd boundary around nvfi_render_mlp / nvfi_render_mlp_grad (include/nvfi_hip.h), built like _AdvectFn.  The forward IS
+    field._render_module_call and saves only the three inputs and the six tensors of renderModule.mlp (none under SH shading): the backward
+    runs the forward again in stash form, chunk by chunk on one workspace of at most `max_ws` bytes (~3 KB per point + 51 MB of slabs), and
+    accumulates the MLP's gradients over the chunks into buffers cleared here."""
+    N_ARGS = 5      # field, pts, viewdirs, features, max_ws
+
+    @staticmethod
+    def forward(ctx, field, pts, viewdirs, features, max_ws, *params):
+        rgb = field._render_module_call(pts, viewdirs, features)
+        ctx.field, ctx.max_ws = field, int(max_ws)
+        ctx.save_for_backward(pts, viewdirs, features, *params)
+        ctx.set_materialize_grads(False)
+        return rgb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ..utils import field_lookup as fl
+        x, v, fe, *params = ctx.saved_tensors
+        if g is None:
+            return (None,) * (_ShadeFn.N_ARGS + len(params))
+        field = ctx.field
+        need = ctx.needs_input_grad[_ShadeFn.N_ARGS:]
+        grads, G = [], None
+        desc = field._desc(field._params_with(fs.RENDER_MLP, params) if params else None)
+        if params and any(need):
+            grads, G = _plain_grads(field, params, need, fs.RENDER_MLP)
+        elif params:
+            grads = [None] * len(params)
+        g = g.reshape(-1, 3).contiguous().float()
+        N = x.shape[0]
+        want_x, want_v, want_f = ctx.needs_input_grad[1:4]
+        gx = torch.empty_like(x) if want_x else None
+        gv = torch.empty_like(v) if want_v else None
+        gf = torch.empty_like(fe) if want_f else None
+        chunk, ws_bytes, chunks = _lib.plan_chunks(lambda n: fl.render_mlp_grad_workspace_bytes(desc, n), N, ctx.max_ws, "shade", unit="point")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        field.last_shade_chunks = chunks
+        field.last_shade_workspace_bytes = ws.numel()
+        for i in range(0, chunks * chunk, max(chunk, 1)):
+            s = slice(i, min(i + chunk, N))
+            fl.render_mlp_grad_raw(desc, x[s], v[s], fe[s], g[s], g_features=None if gf is None else gf[s], g_xyz=None if gx is None else gx[s],
+                                   g_view=None if gv is None else gv[s], grads=G, workspace=ws)
+        return (None, gx, gv, gf, None) + tuple(grads)
+
+
 class _DensityLookupFn(torch.autograd.Function):
     """autograd boundary around nvfi_density_at / nvfi_density_grad (include/nvfi_hip.h).  The forward IS field.compute_densityfeature and saves
     only the points and the six density planes: the backward reads the taps again (no stash) and computes only what autograd asks for."""

@@ -67,6 +67,14 @@ class NVFi(nn.Module):
         """compute_appfeature, forward only (TensorVMKeyframeTimeKplane.compute_appfeature)"""
         return self.nvfi.compute_appfeature(xyzt)
 
+    def shade(self, pts, viewdirs, features, max_workspace_bytes=1 << 30):
+        """renderModule(pts, viewdirs, features) with gradients to all three and to renderModule.mlp (TensorVMKeyframeTimeKplane.shade)"""
+        return self.nvfi.shade(pts, viewdirs, features, max_workspace_bytes=max_workspace_bytes)
+
+    def lookup_rgb(self, xyzt, viewdirs, max_workspace_bytes=1 << 30):
+        """the colour of given points with gradients to the points, the appearance planes, basis_mat and the MLP (TensorVMKeyframeTimeKplane.lookup_rgb)"""
+        return self.nvfi.lookup_rgb(xyzt, viewdirs, max_workspace_bytes=max_workspace_bytes)
+
     def distortion_delta(self):
         """stepSize / (far - near): the interval width the distortion loss takes (TensorVMKeyframeTimeKplane.distortion_delta)"""
         return self.nvfi.distortion_delta()

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import stream_ptr as _stream_ptr
 from . import field_slots as fs
-from .field_autograd import _AdvectFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _PdeFn, _RegFn, _RenderFn
+from .field_autograd import _AdvectFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _PdeFn, _RegFn, _RenderFn, _ShadeFn
 from .field_grads import FieldGrads, _rt, round64
 from .mask_field import _mask_desc
 from .tensorf_model_utils import AlphaGridMask
@@ -54,7 +54,8 @@ class MLPRender_PE(nn.Module):
             raise _lib.NvfiError("MLPRender_PE.forward needs the field it belongs to (it is created by TensorVMKeyframeTimeKplane)")
         if torch.is_grad_enabled() and (features.requires_grad or pts.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("stand-alone MLPRender_PE.forward is forward-only: call it under torch.no_grad() "
-                                      "(gradients of the render module flow through Renderer.render / NVFi.render_ray)")
+                                      "(gradients of the render module flow through Renderer.render / NVFi.render_ray; "
+                                      "at given points, through field.shade / field.lookup_rgb)")
         return field._render_module_call(pts, viewdirs, features)
 
 
@@ -844,6 +845,29 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         _lib.check(L.nvfi_render_mlp(C.byref(desc), C.c_int64(N), _lib.ptr(x), _lib.ptr(v), _lib.ptr(fe), _lib.ptr(rgb), _lib.ptr(ws),
                                      C.c_int64(ws.numel()), _stream_ptr()))
         return rgb
+
+    def shade(self, pts, viewdirs, features, max_workspace_bytes=1 << 30):
+        """renderModule(pts, viewdirs, features) WITH gradients (tensorf_base.py:88-98, or SHRender, under autograd): (N,3), (N,3), (N, app_dim) ->
+        (N,3), differentiable once to `features`, `pts`, `viewdirs` and the six tensors of renderModule.mlp - colour constancy along a trajectory
+        (`advect`), colour supervision from RGB-D point clouds, distillation of radiance, pose / direction refinement.  The value is
+        renderModule's bit for bit; under no_grad, or when nothing requires grad, this IS _render_module_call.  The backward runs the forward again
+        in chunks whose workspace stays under `max_workspace_bytes` (nvfi_render_mlp_grad).  Per-point gradients repeat bit for bit."""
+        if not all(isinstance(a, torch.Tensor) and a.is_cuda for a in (pts, viewdirs, features)):
+            raise _lib.NvfiError("shade needs its points, view directions and features on the GPU (no CPU fallback exists)")
+        mlp = [p for p in self._render_params()[fs.RENDER_MLP] if p is not None]
+        if not (torch.is_grad_enabled() and any(a.requires_grad for a in [pts, viewdirs, features] + mlp)):
+            return self._render_module_call(pts, viewdirs, features)
+        return _ShadeFn.apply(self, pts.reshape(-1, 3).contiguous().float(), viewdirs.reshape(-1, 3).contiguous().float(),
+                              features.reshape(-1, self.app_dim).contiguous().float(), int(max_workspace_bytes), *mlp)
+
+    def lookup_rgb(self, xyzt, viewdirs, max_workspace_bytes=1 << 30):
+        """shade(xyzt[:, :3], viewdirs, lookup_appfeature(xyzt)): the colour of given points (N,4) normalised (x,y,z,t') with gradients to the points
+        (t' included), the six appearance planes, basis_mat.weight and the MLP.  The value is renderModule(xyz, view, compute_appfeature(xyzt))
+        bit for bit; it agrees with app_at only to rounding (app_at forms the features on the MFMA path inside its kernel)."""
+        if not (isinstance(xyzt, torch.Tensor) and xyzt.is_cuda):
+            raise _lib.NvfiError("lookup_rgb needs its points on the GPU (no CPU fallback exists)")
+        q = xyzt.reshape(-1, 4)
+        return self.shade(q[:, :3], viewdirs, self.lookup_appfeature(q), max_workspace_bytes=max_workspace_bytes)
 
     def pde_loss(self, points, t):
         """PDE regulariser on explicit collocation points (world-space (P,3), raw t (P,1)); models/nvfi.py:42-84."""
