@@ -186,7 +186,8 @@ int nvfi_pde_loss_dev(const nvfi_field_desc* f, int64_t P, const float* points, 
 
 /* ---- mask branch of render_pts (models/tensorf_keyframe.py:673-676, 749-753) with the MaskField as train_segm.py:97-102
  *      builds it: 3 -> n_dim x n_layer (ReLU) -> mask_dim, softmax.  Call after nvfi_render_fwd with the same workspace:
- *      mask_map[R][mask_dim] = sum over appearance-masked samples of weight * softmax(MaskField(warped xyz)). Inference only. */
+ *      mask_map[R][mask_dim] = sum over appearance-masked samples of weight * softmax(MaskField(warped xyz)). Inference only
+ *      (a loss on this map with all its gradients: nvfi_mask_loss_fwd / nvfi_mask_loss_bwd below). */
 typedef struct nvfi_mask_desc {
     int32_t n_layer;         /* hidden layers (4) */
     int32_t n_dim;           /* hidden width (128) */
@@ -394,6 +395,60 @@ int nvfi_flow_loss_fwd(const nvfi_field_desc* f, int64_t R, const float* rays_o,
                        void* workspace, int64_t workspace_bytes, void* stream);
 int nvfi_flow_loss_bwd(const nvfi_field_desc* f, int64_t R, float t, float dt, int64_t first, int64_t chunk_cap,
                        const nvfi_grads* grads /* vW / vb ACCUMULATED, the rest ignored */,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- 2-D mask supervision of a render (an addition to ABI v5; csrc/maskloss.hip; not in the reference, which renders the soft label map -
+ *      nvfi_render_mask above - but has no loss on it): the mask map of a render nvfi_render_fwd* made, of R rays at HOST-scalar time t, its loss
+ *      against per-ray labels or soft targets, and all gradients.  K = m->mask_dim.
+ *        M_r   the appearance-masked samples of ray r: the workspace's mlist / off_m AS THE RENDER MADE THEM (w > weight_thres is not re-evaluated)
+ *        x_j   the warped keyframe position the render stored (xw[list[i]].xyz): the points k_mask_fwd of nvfi_render_mask reads
+ *        w_j   the render's fp32 weights
+ *        m_jk  = softmax(MaskField(x_j))_k, the field 3 -> 128 x 4 (ReLU) -> K, 1 <= K <= 32, on the exact-fp32 MFMA (NVFI_MASK_FP16 has no form here)
+ *        q[r][k] (R,K) = sum_{j in M_r} w_j m_jk   summed in list order, no float atomics: the BITS nvfi_render_mask gives on the same workspace and
+ *                        weights; a ray without masked samples gets exact zeros
+ *        targets: with `labels` (device int32 (R)) a label in [0, K) makes y_r one-hot, the label K makes y_r = 0 (background), a negative label
+ *                        IGNORES the ray.  A label above K is a caller's error; the labels are device data, the host cannot look at them before a
+ *                        launch, so on the device such a ray is IGNORED as well.  With `soft` (device float (R,K)) y_r is the row, and a row with a
+ *                        non-finite entry ignores the ray.  Exactly one of the two is given.
+ *        n     = the number of rays that are not ignored; it stays on the device: loss is device float[2] = (loss, n)
+ *        kind 0 (l2): loss = 1 / (2 n K) sum_valid sum_k (q_rk - y_rk)^2
+ *        kind 1 (ce): loss = -(1 / n) sum_valid sum_k y_rk log(q_rk + eps), eps > 0 the caller's; q is NOT renormalised by the ray's opacity; a
+ *                        background ray (y = 0) adds nothing to the value or the gradient but counts in n
+ *        n == 0: loss = 0 and every gradient exactly zero.  The mean is formed in a fixed order with fp64 partials.
+ *      Gradients are grad_scale [* grad_scale_dev[0]] times the following, every discrete decision held fixed:
+ *        g_q[r][k]       = (q - y) / (n K) (l2), -y / ((q + eps) n) (ce), 0 for an ignored ray
+ *        g_weights[r][j] = sum_k g_q[r][k] m_jk for j in M_r, 0 elsewhere; the (R,S) array is WRITTEN, with NVFI_MASKLOSS_ADD_GW in loss_flags ADDED
+ *                          to (composes with the scratch nvfi_ray_distortion and nvfi_flow_loss_fwd share)
+ *        g_mask[j][k]    = w_j g_q[ray(j)][k]; it goes through the softmax and MLP adjoint of nvfi_maskfield_bwd into the ten tensors of
+ *                          nvfi_mask_grads, ACCUMULATED; a NULL member skips that tensor
+ *        Nothing reaches the points x_j (as in nvfi_maskfield_bwd and the host-assembled train-mode mask map): the velocity net and the planes
+ *        get something only through g_weights and the render backward.  No second order.
+ *      nvfi_mask_loss_fwd: behind nvfi_render_fwd* with the same f, R, t, flags - with NVFI_TRAIN or without (an eval-mode workspace has the same
+ *      mlist, off_m and xw); NVFI_WANT_MASK is not required.  render_workspace is READ only and left bit-identical; everything the backward needs
+ *      (per entry the position, the ray index and the weight; per ray g_q; the packed forward and transposed fragments; the masked count) is copied
+ *      into `workspace` (nvfi_mask_loss_workspace_bytes with the SAME R and chunk_cap), which must stay untouched until the last nvfi_mask_loss_bwd of
+ *      the call; those may then run beside or after the render backward.  loss, mask_map, g_weights: each may be NULL.
+ *      nvfi_mask_loss_bwd: the entries [first, first + chunk_cap) of the masked list, clipped on the DEVICE to the masked count: the MaskField forward
+ *      in stash form, the adjoint, the five weight-gradient jobs with the device count; call it for first = 0, chunk_cap, 2 chunk_cap, ... <
+ *      R * n_samples (S = f->n_samples of the forward).  A chunk wholly beyond the masked count launches kernels that exit at once and changes no
+ *      gradient.  chunk_cap is a multiple of 128, one workgroup's points.
+ *      No host synchronisation, the masked count never reaches the host, every clear is a kernel, no float atomics outside the weight-gradient reduce.
+ *      Errors, before any launch: (2) a mask desc that is not 3 -> 128 x 4 -> K <= 32 or lacks a pointer, R <= 0, both or neither of labels / soft, an
+ *      unknown kind / loss_flags, eps <= 0 with ce, a chunk_cap that is not a positive multiple of 128, R * n_samples >= 2^31 - 256, NULL weights or
+ *      render workspace, NVFI_MASKLOSS_ADD_GW without g_weights; in nvfi_mask_loss_bwd also a `first` that is negative, at or beyond R * S or not a
+ *      multiple of chunk_cap, and NULL grads; (4) a workspace that is NULL, too small or not 16-byte aligned.  The render workspace is planned again
+ *      from f, R, flags, t: what nvfi_render_fwd* refuses for them (2, 4) is refused here too. */
+#define NVFI_MASKLOSS_ADD_GW 1
+int nvfi_mask_loss_workspace_bytes(const nvfi_field_desc* f, const nvfi_mask_desc* m, int64_t R, int64_t chunk_cap, int64_t* bytes);
+int nvfi_mask_loss_fwd(const nvfi_field_desc* f, const nvfi_mask_desc* m, int64_t R, float t, int flags,
+                       const float* weights /* (R,S) of the render */,
+                       const int32_t* labels /* (R) or NULL */, const float* soft /* (R,K) or NULL */, int kind, float eps,
+                       float grad_scale, const float* grad_scale_dev /* device float[1] multiplied in, or NULL */, int loss_flags,
+                       float* loss /* device float[2]: un-scaled loss, n; or NULL */, float* mask_map /* (R,K) or NULL */,
+                       float* g_weights /* (R,S) or NULL */,
+                       const void* render_workspace, int64_t render_workspace_bytes, int64_t chunk_cap,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int nvfi_mask_loss_bwd(const nvfi_mask_desc* m, int64_t R, int S, int64_t first, int64_t chunk_cap,
+                       const nvfi_mask_grads* grads /* W / b ACCUMULATED, NULL members skipped */,
                        void* workspace, int64_t workspace_bytes, void* stream);
 int nvfi_adam_step(const nvfi_adam_tensor* t, int n_tensors, float beta1, float beta2, float eps, int64_t step, int zero_grad, void* stream);
 

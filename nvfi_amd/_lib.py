@@ -13,6 +13,7 @@ NVFI_TRAIN, NVFI_WHITE_BG, NVFI_TRANSFER, NVFI_WANT_MASK, NVFI_BWD_FORK, NVFI_WA
 NCOUNTERS = 8
 NVFI_DEPTH_SKIP_HOLES = 1
 NVFI_FLOWLOSS_ADD_GW = 1
+NVFI_MASKLOSS_ADD_GW = 1
 NVFI_DEPTH_LDS_MAX = 16384      # nvfi_depth_loss keeps both maps in LDS up to this many entries (include/nvfi_hip.h)
 
 
@@ -78,6 +79,7 @@ EXPORTS = [
     "nvfi_flow_loss_workspace_bytes", "nvfi_flow_loss_fwd", "nvfi_flow_loss_bwd",
     "nvfi_density_grad", "nvfi_appfeat_at", "nvfi_appfeat_grad",
     "nvfi_render_mlp_grad_workspace_bytes", "nvfi_render_mlp_grad",
+    "nvfi_mask_loss_workspace_bytes", "nvfi_mask_loss_fwd", "nvfi_mask_loss_bwd",
 ]
 
 _LIB = None
@@ -121,6 +123,10 @@ def lib():
         L.nvfi_appfeat_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
         L.nvfi_render_mlp_grad_workspace_bytes.argtypes = [fp, C.c_int64, i64p]
         L.nvfi_render_mlp_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, fp]
+        L.nvfi_mask_loss_workspace_bytes.argtypes = [fp, fp, C.c_int64, C.c_int64, i64p]
+        L.nvfi_mask_loss_fwd.argtypes = [fp, fp, C.c_int64, C.c_float, C.c_int, fp, fp, fp, C.c_int, C.c_float, C.c_float, fp, C.c_int, fp, fp, fp,
+                                         fp, C.c_int64, C.c_int64, fp, C.c_int64, fp]
+        L.nvfi_mask_loss_bwd.argtypes = [fp, C.c_int64, C.c_int, C.c_int64, C.c_int64, fp, fp, C.c_int64, fp]
         _LIB = L
     return _LIB
 

@@ -7,19 +7,9 @@
 // output; the backward walks the transposed fragments and leaves the adjoints in the MFMA register layout for k_wgrad.
 #include "common.h"
 #include "engine16.h"
+#include "maskmlp.h"       // stash rows, fragment sizes and order, slab room: shared with maskloss.hip
 #include <string.h>
 
-#define MK_F_ROWS (16 + 4 * 64 + 16)   // forward stash per tile: x0 (16) | h1..h4 (64 each) | softmax (16)
-#define MK_B_ROWS (16 + 4 * 64)        // backward stash per tile: g_logits (16) | g_z4, g_z3, g_z2, g_z1 (64 each)
-#define MK_NSLAB 256
-#define MK_SLAB_FLOATS (128 * 128 + 128)
-#define MK_F0 (4 * 2 * 64)
-#define MK_FH (4 * 64 * 64)
-#define MK_F4 (1 * 64 * 64)
-#define MK_T4 (4 * 16 * 64)            // transposed last layer: rows = 128 hidden features, slots = 32 logit rows
-#define MK_FRAG_FLOATS (MK_F0 + 3 * MK_FH + MK_F4 + 5 * 128 + MK_T4 + 3 * MK_FH)
-
-struct MkFrags { const float* f[5]; const float* b[5]; const float* t[5]; };   // t[0] unused (no gradient wrt the points)
 struct MkArgs {
     MkFrags W; int mask_dim; int64_t N;
     const float* xyz; float* out;        // (N,3) -> (N,mask_dim)
@@ -27,7 +17,6 @@ struct MkArgs {
     float* stash_f; float* stash_b;
     unsigned* relu_mask;                 // [tile][hidden layer 0..3][lo | hi][64 lanes]: signs of the post-ReLU activations (the adjoint reads these, not the rows)
 };
-#define MK_MASK_WORDS (4 * 128)
 
 template <bool STASH>
 __global__ __launch_bounds__(WG_THREADS, 2) void k_maskfield_fwd(MkArgs a) {
@@ -475,11 +464,7 @@ extern "C" int nvfi_maskfield_bwd(const nvfi_mask_desc* m, int64_t N, const floa
     if (P.total > workspace_bytes) return nvfi_fail(4, "workspace too small (was the forward run with train != 0?)");
     MkArgs a; memset(&a, 0, sizeof(a));
     PackJobs dummy; dummy.n = 0;
-    {   // fragment pointers inside the workspace the forward packed (same layout as mask_frags)
-        float* p = P.frag;
-        for (int l = 0; l < 5; ++l) { const int MT = l < 4 ? 4 : 1, NS = l == 0 ? 2 : 64; a.W.f[l] = p; p += MT * NS * 64; a.W.b[l] = p; p += 128; }
-        for (int l = 1; l < 5; ++l) { const int NS = l < 4 ? 64 : 16; a.W.t[l] = p; p += 4 * NS * 64; }
-    }
+    mk_frag_ptrs(P.frag, &a.W);       // inside the workspace the forward packed (same layout as mask_frags)
     a.mask_dim = m->mask_dim; a.N = N; a.g_out = g_mask; a.stash_f = P.stash_f; a.stash_b = P.stash_b; a.relu_mask = P.relu;
     const unsigned wgs = (unsigned)((N + WG_SAMPLES - 1) / WG_SAMPLES);
     if (mode & NVFI_MASK_FP16) {

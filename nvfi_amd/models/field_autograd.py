@@ -470,3 +470,48 @@ class _FlowLossFn(torch.autograd.Function):
         g_w = call["g_weights"] * g if ctx.needs_input_grad[1] else None
         ctx.call = None
         return (None, g_w) + (None,) * (_FlowLossFn.N_ARGS - 2) + tuple(grads)
+
+
+class _MaskLossFn(torch.autograd.Function):
+    """autograd boundary around nvfi_mask_loss_fwd / nvfi_mask_loss_bwd (include/nvfi_hip.h), built like _FlowLossFn: the forward runs behind
+    the training render whose backward node `node` still holds its workspace and forms the value, the mask map, d loss / d weights and the
+    per-ray g_q in the call's own workspace; the backward runs the MaskField adjoint chunk by chunk on that workspace and hands
+    d loss / d weights to autograd, which carries it into _RenderFn.backward as g_weights.  params: the ten MaskField tensors."""
+    N_ARGS = 8      # field, weights, node, mask_field, target, kind, eps, max_ws
+
+    @staticmethod
+    def forward(ctx, field, weights, node, mask_field, target, kind, eps, max_ws, *params):
+        from ..utils import mask_loss as ml
+        from .mask_field import _mask_desc
+        w_saved = node.saved_tensors[2]
+        desc = field._desc()
+        desc.vel_fp16 = node.vel_fp16
+        params_c = [p.detach().contiguous() for p in params]
+        md = _mask_desc(mask_field, params_c)
+        want_gw = ctx.needs_input_grad[1]
+        call = ml.mask_loss_raw(desc, md, node.ws, node.flags, w_saved, node.t, target, kind=kind, eps=eps,
+                                g_weights=None if want_gw else False, max_workspace_bytes=max_ws)
+        field.last_mask_chunks, field.last_mask_workspace_bytes = call["chunks"], call["workspace"].numel()
+        field.last_mask_map, field.last_mask_n = call["mask_map"], call["loss"][1]
+        ctx.mask_field, ctx.call, ctx.params_c = mask_field, call, params_c
+        return call["loss"][0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from ..utils import mask_loss as ml
+        from .mask_field import _mask_desc
+        call = ctx.call
+        if call is None:
+            raise ValueError("mask_loss: the workspace of this call was released by its first backward; a second backward needs a new mask_loss call")
+        need = ctx.needs_input_grad[_MaskLossFn.N_ARGS:]
+        grads = [torch.zeros_like(p) if n else None for p, n in zip(ctx.params_c, need)]
+        if any(need):
+            ml.mask_loss_backward_raw(_mask_desc(ctx.mask_field, ctx.params_c), call, ml.mask_grads_struct(grads))
+        g = g.detach().float()
+        for gr in grads:                           # the upstream gradient never visits the host
+            if gr is not None:
+                gr.mul_(g)
+        g_w = call["g_weights"] * g if ctx.needs_input_grad[1] else None
+        ctx.call = None
+        return (None, g_w) + (None,) * (_MaskLossFn.N_ARGS - 2) + tuple(grads)

@@ -87,6 +87,10 @@ class NVFi(nn.Module):
         """optical-flow supervision of a training render, with gradient (TensorVMKeyframeTimeKplane.flow_loss)"""
         return self.nvfi.flow_loss(weights, dt, camera, target_flow, **kw)
 
+    def mask_loss(self, weights, target, **kw):
+        """2-D mask supervision of a training render, with gradient (TensorVMKeyframeTimeKplane.mask_loss)"""
+        return self.nvfi.mask_loss(weights, target, **kw)
+
     def update_nvfi_kwargs(self, kwargs):
         """models/nvfi.py:33-35 writes every checkpoint kwarg into the field's __dict__.  Same effect here, except that the two
         entries the C-ABI descriptor caches on the host (aabb, gridSize) go through the buffer / update_stepSize."""

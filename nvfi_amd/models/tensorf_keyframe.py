@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import stream_ptr as _stream_ptr
 from . import field_slots as fs
-from .field_autograd import _AdvectFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _PdeFn, _RegFn, _RenderFn, _ShadeFn
+from .field_autograd import _AdvectFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _MaskLossFn, _PdeFn, _RegFn, _RenderFn, _ShadeFn
 from .field_grads import FieldGrads, _rt, round64
 from .mask_field import _mask_desc
 from .tensorf_model_utils import AlphaGridMask
@@ -31,6 +31,7 @@ _LOSS_DEPTH = 1                # nvfi_depth_loss: the value ...
 _LOSS_DEPTH_COUNT = 2          # ... and its int64 count of the entries that took part (8-byte aligned: two floats)
 _LOSS_DISTORTION = 4           # nvfi_ray_distortion
 _LOSS_FLOW = 6                 # nvfi_flow_loss_fwd: the value and, in the next slot, n (the number of rays that counted)
+_LOSS_MASK = 8                 # nvfi_mask_loss_fwd: the value and, in the next slot, n (the number of rays that are not ignored)
 
 
 class MLPRender_PE(nn.Module):
@@ -1006,7 +1007,8 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
     def render_mse_backward_(self, t, ray_o, ray_d, target, white_bg=True, loss_scale=1.0, jitter=None, wait_before_backward=None,
                              target_depth=None, depth_index=None, depth_weight=1.0, skip_holes=False, check_depth_index=False,
                              distortion_weight=0.0, target_flow=None, flow_dt=None, flow_camera=None, flow_weight=1.0, flow_valid=None,
-                             flow_kind="l2", flow_huber_delta=1.0, flow_max_workspace_bytes=1 << 30):
+                             flow_kind="l2", flow_huber_delta=1.0, flow_max_workspace_bytes=1 << 30,
+                             target_mask=None, mask_field=None, mask_weight=1.0, mask_kind="ce", mask_eps=1e-5, mask_max_workspace_bytes=1 << 30):
         """Fused-driver form of one TRAINING render of train_nvfi.py:150-178 + its share of loss.backward() (train_nvfi.py:242):
         forward, `loss_scale * F.mse_loss(rgb_map, target)` and the backward of both, with the parameter gradients ACCUMULATED into p.grad
         (which must exist: nvfi_amd.dist.GradBucket, or zeros_like) - no autograd graph, no torch launch: nvfi_render_fwd_mse forms the loss and
@@ -1038,12 +1040,25 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         tensor, the pose of flow_camera a float32 device tensor and flow_valid a contiguous uint8 device tensor.  A host pose is copied to the
         device and a bool / float mask converted with a torch launch on every call (utils.flow_loss.flow_loss_raw); convert them once outside
         a loop or a captured graph.  The UN-scaled, un-weighted value (0-dim device tensor) is appended behind the distortion value.  The mask
-        branch and DeviceTime renders raise NotImplementedError."""
+        branch and DeviceTime renders raise NotImplementedError.
+        target_mask (default None: nothing changes, the same launches, return values and refusals): 2-D mask supervision (mask_loss; the
+        definition is in include/nvfi_hip.h) of the MaskField `mask_field` (default self.mask_field): int (R) labels or float (R, K) rows,
+        mask_kind "ce" / "l2".  One nvfi_mask_loss_fwd between the two halves, behind the distortion and flow calls (it then ADDS its
+        `loss_scale * mask_weight * d(mask loss)/d(weights)` to their scratch), and the chunked nvfi_mask_loss_bwd behind the backward half,
+        ACCUMULATED into the .grad of the mask field's ten parameters, which must exist - no torch launch when target_mask arrives as
+        contiguous int32 labels or contiguous float32 rows.  The UN-scaled, un-weighted value (0-dim device tensor) is appended LAST."""
         L = _lib.lib()
         t_dev = getattr(t, "dev", None)
         ray_o, ray_d, t = self._prep_rays(ray_o, ray_d, t)
-        if self.mask_field is not None:
+        if self.mask_field is not None and target_mask is None:
             raise NotImplementedError("render_mse_backward_ does not drive the mask branch")
+        if target_mask is not None:
+            if t_dev is not None:
+                raise NotImplementedError("render_mse_backward_: the mask term does not support DeviceTime renders")
+            mask_field = self._mask_field_arg(mask_field, "render_mse_backward_(target_mask=)")
+            mparams = mask_field._params()
+            if any(p.requires_grad and (p.grad is None or not p.grad.is_contiguous()) for p in mparams):
+                raise _lib.NvfiError("render_mse_backward_(target_mask=) accumulates into the .grad of the mask field's parameters: they must exist")
         distortion_weight = float(distortion_weight)
         if not distortion_weight >= 0.0:
             raise ValueError(f"distortion_weight must not be negative ({distortion_weight})")
@@ -1114,18 +1129,110 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
                                          loss=loss[_LOSS_FLOW:_LOSS_FLOW + 2], flow2d=False, max_workspace_bytes=flow_max_workspace_bytes)
             g_w_flow = flow_call["g_weights"]
             self.last_flow_chunks, self.last_flow_workspace_bytes = flow_call["chunks"], flow_call["workspace"].numel()
+        mask_call = None
+        if target_mask is not None:
+            from ..utils import mask_loss as ml
+            g_prev = g_w if flow_call is None else g_w_flow
+            md = _mask_desc(mask_field, mparams)
+            mask_call = ml.mask_loss_raw(desc, md, ws, flags, weights, t, target_mask, kind=mask_kind, eps=mask_eps,
+                                         grad_scale=float(loss_scale) * float(mask_weight), g_weights=g_prev, add_gw=g_prev is not None,
+                                         loss=loss[_LOSS_MASK:_LOSS_MASK + 2], mask_map=None, max_workspace_bytes=mask_max_workspace_bytes)
+            g_w_mask = mask_call["g_weights"]
+            self.last_mask_map, self.last_mask_n = mask_call["mask_map"], loss[_LOSS_MASK + 1]
+            self.last_mask_chunks, self.last_mask_workspace_bytes = mask_call["chunks"], mask_call["workspace"].numel()
         if wait_before_backward is not None:
             torch.cuda.current_stream().wait_stream(wait_before_backward)
         G = self._grads_struct_cached(ps)
         _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_int(int(t_dev is not None)),
-                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, _lib.ptr(g_w if flow_call is None else g_w_flow), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
+                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, _lib.ptr(g_w_mask if mask_call is not None else g_w if flow_call is None else g_w_flow), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
         res = (loss[_LOSS_MSE], rgb) if g_depth is None else (loss[_LOSS_MSE], rgb, loss[_LOSS_DEPTH])
         if g_w is not None:
             res = res + (loss[_LOSS_DISTORTION],)
         if flow_call is not None:
             fl.flow_loss_backward_raw(desc, flow_call, G)
             res = res + (loss[_LOSS_FLOW],)
+        if mask_call is not None:
+            ml.mask_loss_backward_raw(md, mask_call, ml.mask_grads_struct([p.grad if p.requires_grad else None for p in mparams]))
+            res = res + (loss[_LOSS_MASK],)
         return res
+
+    def _mask_field_arg(self, mask_field, who):
+        mask_field = self.mask_field if mask_field is None else mask_field
+        if mask_field is None:
+            raise ValueError(f"{who} needs a mask_field (the argument or self.mask_field)")
+        if getattr(mask_field, "mfma_fp16", False):
+            raise NotImplementedError(f"{who}: the fp16-input MaskField mode has no loss path (exact fp32 MFMA only)")
+        return mask_field
+
+    def mask_loss(self, weights, target, mask_field=None, kind="ce", eps=1e-5, weight_grad=True, max_workspace_bytes=1 << 30):
+        """2-D mask supervision of a training render (include/nvfi_hip.h: nvfi_mask_loss_fwd / _bwd; utils/mask_loss.py) -> 0-dim loss with
+        gradient.  `weights` must be the (R, S) tensor that a training `forward` of this field returned - the tensor itself, with its autograd
+        node, whose workspace (masked list, warped positions) the call reads; anything else, or a render whose backward has already run,
+        raises ValueError, a DeviceTime render NotImplementedError.  It need not be the most recent render.
+        mask_map[r] = sum_j w_j softmax(mask_field(x_j)) over the render's appearance-masked samples (mask_field defaults to self.mask_field;
+        the render need not have been made with it attached).  target: int (R) labels - [0, K) one-hot, K background, negative ignored - or
+        float (R, K) rows (a row with a non-finite entry is ignored).  kind "l2": 1 / (2 n K) sum (mask_map - y)^2; "ce": -(1 / n) sum y
+        log(mask_map + eps); n the number of rays that are not ignored.
+        The gradient reaches the weights (and through the render backward everything the render depends on; weight_grad=False leaves the
+        weights without gradient) and the ten MaskField parameters; the points carry none, no second order.  The backward splits the
+        R * nSamples capacity of the masked list into chunks whose plan stays under max_workspace_bytes (self.last_mask_chunks,
+        self.last_mask_workspace_bytes).  self.last_mask_map holds the (R, K) map, self.last_mask_n the device-side count of rays."""
+        mask_field = self._mask_field_arg(mask_field, "mask_loss")
+        if not (isinstance(weights, torch.Tensor) and weights.is_cuda):
+            raise _lib.NvfiError("mask_loss needs the weights of a render on the GPU (no CPU fallback exists)")
+        node = weights.grad_fn
+        if not isinstance(node, _RenderFn._backward_cls) or getattr(node, "field", None) is not self or not (getattr(node, "flags", 0) & _lib.NVFI_TRAIN):
+            raise ValueError("mask_loss: `weights` must be the tensor a training forward of this field returned (with its autograd node)")
+        if node.ws is None:
+            raise ValueError("mask_loss: the workspace of that render was released by its backward; call mask_loss before backward")
+        if node.t_on_device:
+            raise NotImplementedError("mask_loss: DeviceTime renders are not supported (the mask loss plans with a host-scalar time)")
+        w_in = weights if (weight_grad and torch.is_grad_enabled()) else weights.detach()
+        return _MaskLossFn.apply(self, w_in, node, mask_field, target, kind, float(eps), int(max_workspace_bytes), *mask_field._params())
+
+    @torch.no_grad()
+    def mask_fit_backward_(self, t, ray_o, ray_d, target_mask, mask_field=None, kind="ce", eps=1e-5, loss_scale=1.0, white_bg=True, jitter=None,
+                           max_workspace_bytes=1 << 30, workspace=None):
+        """The frozen-scene step of fitting a MaskField to 2-D masks of a trained scene: an eval-mode render of the rays (no training stash,
+        no render backward), the mask loss of its masked samples with no weight gradient, and the chunked MaskField backward ACCUMULATED
+        into the .grad of the mask field's ten parameters (which must exist), scaled by loss_scale.  Three library calls plus one per
+        chunk; no torch launch and no host synchronisation when target_mask arrives as contiguous int32 labels or float32 (R, K) rows, so
+        the step can be captured in a graph.  jitter (default None: the eval render's fixed samples and alpha-mask cull): a per-ray sample
+        offset in [0, 1); the library jitters only renders flagged NVFI_TRAIN, so with a jitter the render is made in training mode - the
+        training sampling rules, and a workspace that holds the training stash nobody reads.
+        Workspace: the masked count stays on the device, so the plan covers the R * nSamples CAPACITY of the masked list - the largest chunk
+        whose plan stays under max_workspace_bytes (default 1 GiB; 2 048 x 128 rays take all of it, in two chunks, whatever the count is:
+        self.last_mask_chunks, self.last_mask_workspace_bytes).  A fit loop should lower max_workspace_bytes to a few chunks' worth and pass
+        `workspace`, a uint8 device tensor of at least utils.mask_loss.mask_loss_plan(...)[1] bytes that it keeps across steps (nothing in
+        it outlives the call); without it every call allocates the plan afresh.
+        Returns (loss, mask_map): the UN-scaled 0-dim value and the (R, K) map; self.last_mask_n is the device-side count of rays."""
+        from ..utils import mask_loss as ml
+        L = _lib.lib()
+        mask_field = self._mask_field_arg(mask_field, "mask_fit_backward_")
+        if getattr(t, "dev", None) is not None:
+            raise NotImplementedError("mask_fit_backward_: DeviceTime renders are not supported")
+        mparams = mask_field._params()
+        if any(p.requires_grad and (p.grad is None or not p.grad.is_contiguous()) for p in mparams):
+            raise _lib.NvfiError("mask_fit_backward_ accumulates into the .grad of the mask field's parameters: they must exist")
+        ray_o, ray_d, t = self._prep_rays(ray_o, ray_d, t)
+        R = ray_o.shape[0]
+        flags = _lib.NVFI_WHITE_BG if white_bg else 0
+        if jitter is not None:
+            flags |= _lib.NVFI_TRAIN
+            jitter = jitter.reshape(-1).float().contiguous()
+        desc, ws, (rgb, depth, acc, weights, counters) = self._ray_buffers(R, ray_o.device, t, flags)
+        st = _stream_ptr()
+        _lib.check(L.nvfi_render_fwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(jitter), C.c_float(t), None,
+                                       C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws),
+                                       C.c_int64(ws.numel()), _lib.ptr(counters), st))
+        self.last_counters = counters
+        md = _mask_desc(mask_field, mparams)
+        call = ml.mask_loss_raw(desc, md, ws, flags, weights, t, target_mask, kind=kind, eps=eps, grad_scale=float(loss_scale), g_weights=False,
+                                max_workspace_bytes=int(max_workspace_bytes), workspace=workspace)
+        ml.mask_loss_backward_raw(md, call, ml.mask_grads_struct([p.grad if p.requires_grad else None for p in mparams]))
+        self.last_mask_map, self.last_mask_n = call["mask_map"], call["loss"][1]
+        self.last_mask_chunks, self.last_mask_workspace_bytes = call["chunks"], call["workspace"].numel()
+        return call["loss"][0], call["mask_map"]
 
     def flow_loss(self, weights, dt, camera, target_flow, valid=None, kind="l2", huber_delta=1.0, weight_grad=True, max_workspace_bytes=1 << 30):
         """Optical-flow supervision of a training render (include/nvfi_hip.h: nvfi_flow_loss_fwd / _bwd; utils/flow_loss.py) -> 0-dim loss
