@@ -52,6 +52,23 @@ def make_model(kind, device="cuda", use_vel=True):
     return m, meta
 
 
+def sh_model(device="cuda"):
+    """field D of tests/golden/r2.npz: field A's geometry with shadingMode "SH" (app_dim 27, basis_mat 48 -> 27, no render MLP)"""
+    from nvfi_amd.models import NVFi
+    g2 = np.load(os.path.join(GOLD, "r2.npz"))
+    meta = load_meta("A")[0]
+    cfg = field_cfg(meta)
+    cfg.nvfi.shadingMode = "SH"
+    cfg.nvfi.app_dim = 27
+    aabb = torch.tensor(np.asarray(meta["aabb"]).reshape(2, 3), dtype=torch.float32)
+    m = NVFi(cfg, "cpu", aabb, [int(g) for g in meta["gridSize"]], [float(meta["near"]), float(meta["far"])])
+    own = m.state_dict()
+    for k in g2.files:
+        if k.startswith("D:sd:") and k[5:] in own:
+            own[k[5:]].copy_(torch.from_numpy(np.ascontiguousarray(g2[k])))
+    return m.to(device)
+
+
 def named_grads(model):
     """{reference parameter name: grad (numpy, logical NCHW)} skipping the duplicated vel.vel_net keys."""
     out = {}

@@ -200,14 +200,7 @@ def density64(field, xyzt, dtype=torch.float64, device="cpu", wrong=False):
     return dict(feat=feat.cpu().numpy(), sigma=sigma.cpu().numpy())
 
 
-def _sh(view, feat27, wrong):
-    C0, C1 = 0.28209479177387814, 0.4886025119029199
-    C2 = [1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396]
-    x, y, z = view[:, 0], view[:, 1], view[:, 2]
-    xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
-    b6 = (zz - xx - yy) if wrong else (2.0 * zz - xx - yy)
-    b = torch.stack([torch.full_like(x, C0), -C1 * y, C1 * z, -C1 * x, C2[0] * xy, C2[1] * yz, C2[2] * b6, C2[3] * xz, C2[4] * (xx - yy)], 1)
-    return torch.relu((b[:, None, :] * feat27.view(-1, 3, 9)).sum(-1) + 0.5)
+_sh = r64._sh          # the one statement of the degree-2 basis
 
 
 def sh64(view, feat27, dtype=torch.float64, device="cpu", wrong=False):

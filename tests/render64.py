@@ -37,6 +37,12 @@ in an eval call (jitter None) an in-box sample stays valid only where the trilin
 read at the FIELD's normalised coordinates - sample_alpha's own normalize_coord is commented out in the reference - so a mask that was built before
 shrink() is read in the new box's coordinates (tests/alpha64.py: sample_alpha64 holds the lookup and says which samples sit on a voxel boundary).
 
+shadingMode "SH" (tensorf_base.py:196-197; SHRender, tensorf_model_utils.py:292-296, sh.py:87-110): app_dim = 27, basis_mat is 48 -> 27 and the
+colour of a masked sample is relu(sum_k SH_k(view) feat[9 c + k] + 0.5) with the degree-2 real basis on the RAW view direction (_sh_basis) - no
+positional encoding, no MLP, no sigmoid: the colour is unbounded above, so the clamp(0, 1) of the composite is live in this mode.  Such a field
+(`Field.sh`) has no renderModule.* parameter: `Field.names` leaves the six out.  `wrong=True` is the one deliberately wrong variant of this file
+(SH fields only): basis 6 formed with zz - xx - yy instead of 2 zz - xx - yy; both test files show that their bounds see it.
+
 Parameters are keyed by the reference's names without the `nvfi.` prefix, as helpers.named_grads gives them."""
 import numpy as np
 import torch
@@ -50,15 +56,18 @@ VEL_NAMES = pde64.NAMES[:12]
 PLANE_NAMES = [f"{b}_plane_{st}.{i}" for b in ("density", "app") for st in ("space", "time") for i in range(3)]
 MLP_NAMES = [f"renderModule.mlp.{i}.{wb}" for i in (0, 2, 4) for wb in ("weight", "bias")]
 NAMES = PLANE_NAMES + ["basis_mat.weight"] + MLP_NAMES + VEL_NAMES
+SH_NAMES = [n for n in NAMES if n not in MLP_NAMES]          # an SH field: basis_mat.weight stays in family `mlp`
 FAMILY = {n: ("density" if n.startswith("density") else "app" if n.startswith("app") else "vel" if n.startswith("vel_net") else "mlp") for n in NAMES}
 
 
 class Field:
     """the parameters (fp32 values, reference layout) and the configuration scalars that reach the render"""
 
-    def __init__(self, sd, meta):
+    def __init__(self, sd, meta, sh=None):
         sd = {(k[5:] if k.startswith("nvfi.") else k): np.asarray(v) for k, v in sd.items()}
-        self.p32 = {k: torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)) for k in NAMES}
+        # SH shading: said by the caller, or read off the parameters (basis_mat 48 -> 27 and no render MLP)
+        self.sh = (tuple(sd["basis_mat.weight"].shape) == (27, 48) and not any(k.startswith("renderModule.") for k in sd)) if sh is None else bool(sh)
+        self.p32 = {k: torch.from_numpy(np.ascontiguousarray(sd[k], dtype=np.float32)) for k in NAMES if not (self.sh and k in MLP_NAMES and k not in sd)}
         m = meta
         self.aabb = torch.from_numpy(np.asarray(m["aabb"], np.float32).reshape(2, 3).copy())
         self.near, self.far = float(m["near"]), float(m["far"])
@@ -75,18 +84,26 @@ class Field:
             self.lo = torch.full((3,), float(np.float32(-1 + eps)), dtype=torch.float32)
             self.hi = torch.full((3,), float(np.float32(1 - eps)), dtype=torch.float32)
 
+    @property
+    def names(self):
+        """the parameters a render of this field can reach (NAMES; without the render MLP's on an SH field)"""
+        return SH_NAMES if self.sh else NAMES
+
 
 class Loss:
     """mse(rgb, target) + w_depth mean(depth) + w_acc mean(acc^2) + sum(weight * gw), as per-ray terms"""
 
-    def __init__(self, target, w_depth=0.0, w_acc=0.0, gw=None):
+    def __init__(self, target, w_depth=0.0, w_acc=0.0, gw=None, keep=None):
+        """keep (R, 3) bool: the channels whose mse term is kept (default: all) - what a test cuts to show that a channel carries no gradient"""
+        self.keep = None if keep is None else torch.as_tensor(np.asarray(keep, bool)).reshape(-1, 3)
         self.target = torch.as_tensor(np.asarray(target, np.float32)).reshape(-1, 3)
         self.w_depth, self.w_acc = float(w_depth), float(w_acc)
         self.gw = None if gw is None else torch.as_tensor(np.asarray(gw, np.float32))
 
     def __call__(self, rgb, depth, acc, weight, idx, R):
         tg = self.target[idx].to(rgb)
-        out = ((rgb - tg) ** 2).sum(-1) / (3 * R)
+        sq = (rgb - tg) ** 2
+        out = (sq if self.keep is None else sq * self.keep[idx].to(rgb)).sum(-1) / (3 * R)
         if self.w_depth:
             out = out + self.w_depth * depth / R
         if self.w_acc:
@@ -172,13 +189,35 @@ def _pe(q, n):
     return torch.cat([torch.sin(f), torch.cos(f)], -1)
 
 
+def _sh_basis(view, wrong=False):
+    """(n, 9): the real spherical harmonics of degree <= 2 at the raw (un-normalised) view direction, in sh.py's order and signs"""
+    C0, C1 = 0.28209479177387814, 0.4886025119029199
+    C2 = [1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396]
+    x, y, z = view[:, 0], view[:, 1], view[:, 2]
+    xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
+    b6 = (zz - xx - yy) if wrong else (2.0 * zz - xx - yy)
+    return torch.stack([torch.full_like(x, C0), -C1 * y, C1 * z, -C1 * x, C2[0] * xy, C2[1] * yz, C2[2] * b6, C2[3] * xz, C2[4] * (xx - yy)], 1)
+
+
+def _sh_pre(view, feat27, wrong=False):
+    """(n, 3, 9) terms SH_k(view) feat[9 c + k] and (n, 3) their sum + 0.5, the colour before its ReLU"""
+    terms = _sh_basis(view, wrong)[:, None, :] * feat27.view(-1, 3, 9)
+    return terms, terms.sum(-1) + 0.5
+
+
+def _sh(view, feat27, wrong):
+    """SHRender: relu(sum_k SH_k(view) feat[9 c + k] + 0.5), (n, 3).  wrong: basis 6 with zz - xx - yy instead of 2 zz - xx - yy"""
+    return torch.relu(_sh_pre(view, feat27, wrong)[1])
+
+
 def _mlp_in(P, x4m, view):
     feat = F.linear(_planes(P, "app", x4m).T, P["basis_mat.weight"])
     xm = x4m[:, :3]
     return torch.cat([feat, view, xm, _pe(xm, 6), _pe(view, 6)], -1)
 
 
-def _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None):
+def _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None,
+           wrong=False):
     """one chunk of rays sl (index array): the maps, the masks, the per-ray loss terms (a tensor still attached to the graph)"""
     idx = torch.as_tensor(sl, dtype=torch.long)
     valid = smp["valid"][idx].to(device)
@@ -223,10 +262,17 @@ def _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, 
         pm = pos[mi]
         x4m = torch.where((pm >= 0)[:, None], x4[pm.clamp(min=0)],
                           torch.cat([xn.reshape(-1, 3)[mi], torch.full_like(xn.reshape(-1, 3)[mi][:, :1], plan["tn_base"])], 1))
-        h = _mlp_in(P, x4m, view[:, None, :].expand(r, S, 3).reshape(-1, 3)[mi])
-        if want_margin:
-            margin = torch.full((mi.numel(),), float("inf"), dtype=dtype, device=device)
-        for i in (0, 2, 4):
+        vm = view[:, None, :].expand(r, S, 3).reshape(-1, 3)[mi]
+        if field.sh:
+            terms_sh, pre = _sh_pre(vm, F.linear(_planes(P, "app", x4m).T, P["basis_mat.weight"]), wrong)
+            if want_margin:       # |pre| over the fp32 rounding bound of its ten-term sum (nine products and the 0.5), per channel
+                margin = (pre.abs() / ((terms_sh.abs().sum(-1) + 0.5) * (2.0 ** -24 * 10))).detach()
+            h = torch.relu(pre)
+        else:
+            h = _mlp_in(P, x4m, vm)
+            if want_margin:
+                margin = torch.full((mi.numel(),), float("inf"), dtype=dtype, device=device)
+        for i in () if field.sh else (0, 2, 4):
             W, b = P[f"renderModule.mlp.{i}.weight"], P[f"renderModule.mlp.{i}.bias"]
             zz = F.linear(h, W, b)
             if want_margin and i < 4:
@@ -242,14 +288,24 @@ def _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, 
     rgb_map = (weight[..., None] * rgb).sum(-2)
     if white_bg:
         rgb_map = rgb_map + (1.0 - acc[..., None])
+    rgb_pre = rgb_map
     rgb_map = rgb_map.clamp(0, 1)
     depth = (weight * z).sum(-1) + (1.0 - acc) * field.far
     terms = loss(rgb_map, depth, acc, weight, idx, R) if loss is not None else None
     res = dict(rgb=rgb_map, depth=depth, acc=acc, weight=weight, app_mask=mask, own_mask=own, valid=valid, in_gate=in_gate.view(r, S))
     if margin is not None:
-        mg = torch.full((r * S,), float("inf"), dtype=dtype, device=device)
+        mg = torch.full((r * S,) + tuple(margin.shape[1:]), float("inf"), dtype=dtype, device=device)
         mg[mi] = margin
-        res["margin"] = mg.view(r, S)
+        res["margin"] = mg.view((r, S) + tuple(margin.shape[1:]))
+    if want_margin and field.sh:
+        # the distance of the composited colour from the two kinks of clamp(0, 1) over the fp32 rounding bound of the composite: S products w c
+        # and the background term.  A channel that sits EXACTLY on a kink because nothing was added to it (a ray without weight: 0 on black, 1 on
+        # white) has no decision to take - every colour gradient of it is multiplied by a zero weight - and is left at inf.
+        comp = ((weight[..., None] * rgb).abs().sum(-2) + ((1.0 - acc[..., None]).abs() if white_bg else 0.0)) * (2.0 ** -24 * (S + 1))
+        dist = torch.minimum(rgb_pre.abs(), (rgb_pre - 1.0).abs())
+        mr = torch.where((dist == 0) & (acc[..., None] == 0), torch.full_like(dist, float("inf")), dist / comp.clamp(min=1e-300))
+        res["margin_ray"] = mr.detach()
+        res["dead"] = (mask[..., None] & (rgb.detach() == 0)) if mi.numel() else torch.zeros(r, S, 3, dtype=torch.bool, device=device)
     return res, terms
 
 
@@ -257,7 +313,8 @@ MAP_KEYS = ("rgb", "depth", "acc", "weight", "app_mask", "own_mask", "valid", "i
 
 
 def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=None, transfer=False, grads=True, rays=None, chunk=256,
-             dtype=torch.float64, device="cpu", cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None, alpha_volume=None, cull_flip=None):
+             dtype=torch.float64, device="cpu", cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None, alpha_volume=None, cull_flip=None,
+             wrong=False):
     """the render of the rays `rays` (default: all; the sampling and the loss's 1 / R always refer to the full batch) -> dict of the maps (numpy),
     `loss_rays` (per-ray loss terms, float64), `loss` (their sum), `grads` {name: float64 array, or None where the parameter is not reached},
     `flips` (indices (ray, sample) where the given app_mask differs from the yardstick's own) and `flip_dist` (their |w - thres|).
@@ -284,13 +341,14 @@ def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=Non
     plan = time_plan(field, t, transfer)
     rays = np.arange(R) if rays is None else np.asarray(rays, np.int64)
     P = {k: v.detach().to(device=device, dtype=dtype, copy=True).requires_grad_(grads and loss is not None) for k, v in field.p32.items()}
-    names = [n for n in NAMES if not (n.startswith("vel_net") and not plan["steps"])]
+    assert not wrong or field.sh, "the wrong variant is the SH basis's"
+    names = [n for n in field.names if not (n.startswith("vel_net") and not plan["steps"])]
     g = {n: torch.zeros(P[n].shape, dtype=torch.float64, device=device) for n in names}
-    outs = {k: [] for k in MAP_KEYS + ("loss_rays",) + (("margin",) if want_margin else ())}
+    outs = {k: [] for k in MAP_KEYS + ("loss_rays",) + (("margin",) if want_margin else ()) + (("margin_ray", "dead") if want_margin and field.sh else ())}
     for s in range(0, len(rays), chunk):
         sl = rays[s:s + chunk]
         with torch.set_grad_enabled(grads and loss is not None):
-            res, terms = _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb, cut_sigma, want_margin, cut_warp)
+            res, terms = _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb, cut_sigma, want_margin, cut_warp, wrong)
             if terms is not None and grads:
                 gi = torch.autograd.grad(terms.sum(), [P[n] for n in names], allow_unused=True)
                 for n, x in zip(names, gi):
@@ -306,12 +364,12 @@ def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=Non
     if cull is not None:
         out.update(cull)
     out["loss"] = float(out["loss_rays"].sum())
-    out["grads"] = {n: (g[n].cpu().numpy() if n in g else None) for n in NAMES} if (grads and loss is not None) else None
+    out["grads"] = {n: (g[n].cpu().numpy() if n in g else None) for n in field.names} if (grads and loss is not None) else None
     diff = out["app_mask"] != out["own_mask"]
     out["flips"] = np.argwhere(diff)
     out["flip_dist"] = np.abs(out["weight"][diff].astype(np.float64) - field.thres)
     out["call"] = dict(field=field, rays_o=rays_o, rays_d=rays_d, t=t, jitter=jitter, white_bg=white_bg, loss=loss, transfer=transfer, chunk=chunk,
-                       dtype=dtype, device=device, alpha_volume=alpha_volume, cull_flip=cull_flip)
+                       dtype=dtype, device=device, alpha_volume=alpha_volume, cull_flip=cull_flip, wrong=wrong)
     return out
 
 
@@ -326,7 +384,7 @@ def with_mask(ref, app_mask):
     full_old = np.zeros((ref["R"], ref["app_mask"].shape[1]), bool)
     full_old[rays] = ref["app_mask"]
     kw = dict(loss=c["loss"], transfer=c["transfer"], chunk=c["chunk"], dtype=c["dtype"], device=c["device"], rays=rays[rows],
-              alpha_volume=c["alpha_volume"], cull_flip=c["cull_flip"])
+              alpha_volume=c["alpha_volume"], cull_flip=c["cull_flip"], wrong=c["wrong"])
     old = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], app_mask=full_old, **kw)
     new = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], app_mask=np.asarray(app_mask, bool), **kw)
     out = dict(ref)
@@ -358,17 +416,21 @@ def detach(ref, samples, branch):
     mask = np.zeros((ref["R"], S), bool)
     mask[rays] = ref["app_mask"]
     kw = dict(app_mask=mask, loss=c["loss"], transfer=c["transfer"], chunk=c["chunk"], dtype=c["dtype"], device=c["device"], rays=rays[rows],
-              alpha_volume=c["alpha_volume"], cull_flip=c["cull_flip"])
+              alpha_volume=c["alpha_volume"], cull_flip=c["cull_flip"], wrong=c["wrong"])
     a = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], **kw)
     b = render64(c["field"], c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], **kw, **{"cut_" + branch: cut})
     return {n: (None if v is None else v - a["grads"][n] + b["grads"][n]) for n, v in ref["grads"].items()}
 
 
-def relu_margin(field, rays_o, rays_d, t, jitter, app_mask=None, chunk=256, device="cpu"):
+def relu_margin(field, rays_o, rays_d, t, jitter, app_mask=None, chunk=256, device="cpu", white_bg=True):
     """(R, S): per appearance-masked sample the smallest |z| / (fp32 rounding bound of z) over the 256 hidden units of the render MLP, inf elsewhere.
-    Below ~1 an fp32 evaluation may take the other side of a ReLU kink than float64, and the sample's parameter gradient jumps there."""
-    r = render64(field, rays_o, rays_d, t, jitter, True, app_mask=app_mask, loss=None, grads=False, chunk=chunk, device=device, want_margin=True)
-    return r["margin"]
+    Below ~1 an fp32 evaluation may take the other side of a ReLU kink than float64, and the sample's parameter gradient jumps there.
+    An SH field has two kinds of kink and returns a pair: (R, S, 3), per masked sample and channel |pre| / (2^-24 x 10 x (sum_k |SH_k feat_k| + 0.5)),
+    pre the colour before its ReLU; and (R, 3), per ray and channel, the distance of the composited colour before clamp(0, 1) from 0 and from 1
+    over 2^-24 x (S + 1) x (sum_s |w c| + |1 - acc|) (inf for a ray without any weight, which sits on its background exactly).  The render64
+    result of an SH field with want_margin also holds `dead` (R, S, 3): the masked (sample, channel) colours that are exactly 0."""
+    r = render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=app_mask, loss=None, grads=False, chunk=chunk, device=device, want_margin=True)
+    return (r["margin"], r["margin_ray"]) if field.sh else r["margin"]
 
 
 def list_order(mask):

@@ -15,6 +15,14 @@ Cases:
                            8192, 8193 golden rays repeated under fresh jitter (PROLOGUE_MAX_RAYS = 8192), autograd path
   big686                   the largest shipped configuration (199^3, 686 samples per ray): the 2048-ray chunk runs, a fixed 256-ray subset is the case
   big_preact               field B with the render MLP's first layer x 2.5 and hidden layer x 4, 256 rays that keep 4 x the rounding bound from a kink
+SH shading (scene `D`: helpers.sh_model, field A's geometry with shadingMode "SH"; `Dclamp`: the same with basis_mat.weight x 12; K = 4, tmax = 0.75):
+  shD_nonkey / shD_key / shD_extrap     the 256 golden rays of field A through forward() + backward() with the golden-style loss at t = 19/60 (one
+                           RK2 step), t = 0.25 (a keyframe) and t = 0.95 (past tmax, two RK2 steps)
+  shD_fused_nonkey / shD_fused_key      the same rays through render_mse_backward_ (the six render-MLP slots of the gradient struct are empty)
+  shm<N> / shr<N>          as m<N> / r<N>, on scene D with the pool of field A's rays
+  shclamp / shclamp_fused  scene Dclamp, 256 rays of a 512-ray pool (the golden rays of field A under fresh jitter): a quarter of the composited
+                           channels sit at the upper clamp, a fifth of the sample colours are dead; rays with a sample or channel within 4 x its
+                           rounding bound of a kink (render64.relu_margin's SH form) are replaced by the next of the pool, and counted
 In the small selections (N <= 129) only rays are used whose weights all keep 1.2e-5 from the appearance threshold on the device."""
 import os
 import sys
@@ -26,6 +34,9 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
 
 T_NONKEY, T_KEY, T_EXTRAP = 19.0 / 60.0, 0.3, 0.83
+T_KEY_A, T_EXTRAP_A = 0.25, 0.95          # field A's geometry (K = 4, tmax = 0.75): a keyframe, and a time past tmax two RK2 steps from it
+CLAMP_SCALE, CLAMP_POOL = 12.0, 512
+RAYS_OF = {"D": "A", "Dclamp": "A"}       # the golden rays a scene is looked at through
 _models = {}
 _pool = {}
 
@@ -53,6 +64,12 @@ def scene(kind, device):
             last.weight.mul_(6.0); last.bias.copy_(torch.tensor([0.5, -0.3, 0.2, 0.1, -0.2, 0.4]))
         m = m.to(device)
         assert m.nvfi.nSamples == 686, m.nvfi.nSamples
+    elif kind in ("D", "Dclamp"):
+        from helpers import sh_model
+        m = sh_model(device)
+        if kind == "Dclamp":           # SH colours far over 1 and far under 0: the clamp of the composite and the dead ReLU are taken
+            with torch.no_grad():
+                m.nvfi.basis_mat.weight.mul_(CLAMP_SCALE)
     else:
         m, _ = make_model("B" if kind == "bigz" else kind, device)
         if kind == "bigz":             # large pre-activations of the render MLP: first layer x 2.5, hidden layer x 4
@@ -77,6 +94,7 @@ def pool_rays(kind="B", reps=6):
         o, d = head_rays()
         return o, d, np.random.default_rng(5).uniform(0, 1, (o.shape[0], 1)).astype(np.float32)
     from conftest import GOLD
+    kind = RAYS_OF.get(kind, kind)
     z = np.load(os.path.join(GOLD, "hotpath.npz"))
     o, d = np.tile(z[f"{kind}:rays_o"], (reps, 1)), np.tile(z[f"{kind}:rays_d"], (reps, 1))
     rng = np.random.default_rng(11)
@@ -94,12 +112,12 @@ def pool_rays(kind="B", reps=6):
     return (np.concatenate([og, o]), np.concatenate([dg, d]), np.concatenate([rng.uniform(0, 1, (768, 1)).astype(np.float32), u]))
 
 
-def big_rays(N):
-    """N rays for the ray-count cases: the golden rays of field B, repeated under fresh jitter"""
+def big_rays(N, kind="B"):
+    """N rays for the ray-count cases: the golden rays of field B (or `kind`), repeated under fresh jitter"""
     from conftest import GOLD
     z = np.load(os.path.join(GOLD, "hotpath.npz"))
     reps = (N + 255) // 256
-    o, d = np.tile(z["B:rays_o"], (reps, 1))[:N], np.tile(z["B:rays_d"], (reps, 1))[:N]
+    o, d = np.tile(z[f"{kind}:rays_o"], (reps, 1))[:N], np.tile(z[f"{kind}:rays_d"], (reps, 1))[:N]
     return o, d, np.random.default_rng(13).uniform(0, 1, (N, 1)).astype(np.float32)
 
 
@@ -125,7 +143,8 @@ def _run(name, kind, o, d, u, t, fused, out):
     od, dd, ud, tg = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (o, d, u, target))
     if fused:
         for p in f._render_params():
-            p.grad = torch.zeros_like(p)
+            if p is not None:          # (an SH field: the six render-MLP slots are empty)
+                p.grad = torch.zeros_like(p)
         loss, rgb = f.render_mse_backward_(t, od, dd, tg, white_bg=True, jitter=ud.reshape(-1))
         torch.cuda.synchronize()
         maps = dict(rgb=rgb)
@@ -200,8 +219,43 @@ def pool(kind="B"):
     return _pool[kind]
 
 
+def clamp_rays(fld):
+    """the 256 rays of shclamp and how many pool rays were passed over: decided by the yardstick alone (CPU or device, float64)"""
+    import render64
+    o, d, u = big_rays(CLAMP_POOL, "A")
+    ms, mr = render64.relu_margin(fld, o, d, T_NONKEY, u, device="cuda" if torch.cuda.is_available() else "cpu")
+    good = (ms > 4.0).all((1, 2)) & (mr > 4.0).all(1)
+    ok = np.nonzero(good)[0][:256]
+    assert len(ok) == 256, len(ok)
+    return o[ok], d[ok], u[ok], int(ok[-1] + 1 - 256), int(ok[-1] + 1)
+
+
+def run_sh_case(name, out):
+    from helpers import field_state, select_rays
+    import render64
+    if name.startswith("shD_"):
+        o, d = (np.load(os.path.join(root, "tests", "golden", "hotpath.npz"))[f"A:rays_{k}"] for k in "od")
+        u = np.random.default_rng(17).uniform(0, 1, (o.shape[0], 1)).astype(np.float32)
+        t = {"nonkey": T_NONKEY, "key": T_KEY_A, "extrap": T_EXTRAP_A}[name.split("_")[-1]]
+        return _run(name, "D", o, d, u, t, "_fused_" in name, out)
+    if name.startswith("shclamp"):
+        o, d, u, redrawn, seen = clamp_rays(render64.Field(*field_state(model("Dclamp"))))
+        out[f"{name}:redrawn"], out[f"{name}:pool_seen"] = np.int64(redrawn), np.int64(seen)
+        return _run(name, "Dclamp", o, d, u, T_NONKEY, name.endswith("_fused"), out)
+    N = int(name[3:])
+    p = pool("D")
+    if name[2] == "r":
+        sel = 768 + np.arange(N)
+    else:
+        sel = select_rays(p["masked"], N, (p["valid"] > 0) & (p["clear"] if N <= 129 else True))
+        assert sel is not None, (name, "no selection of pool rays reaches the count")
+    _run(name, "D", p["o"][sel], p["d"][sel], p["u"][sel], T_NONKEY, False, out)
+
+
 def run_case(name, out):
     from helpers import select_rays
+    if name.startswith("sh"):
+        return run_sh_case(name, out)
     if name.startswith("head_"):
         o, d = head_rays()
         u = np.random.default_rng(5).uniform(0, 1, (o.shape[0], 1)).astype(np.float32)

@@ -15,6 +15,7 @@ import torch
 
 import char64 as c64
 from conftest import GOLD
+from helpers import sh_model          # (the point tests import it from here)
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 65, 1000)
@@ -62,23 +63,6 @@ def ctx_of(kind):
     c.ratios = {}
     _CTX[kind] = c
     return c
-
-
-def sh_model():
-    from helpers import field_cfg, load_meta
-    from nvfi_amd.models import NVFi
-    g2 = np.load(os.path.join(GOLD, "r2.npz"))
-    meta = load_meta("A")[0]
-    cfg = field_cfg(meta)
-    cfg.nvfi.shadingMode = "SH"
-    cfg.nvfi.app_dim = 27
-    aabb = torch.tensor(np.asarray(meta["aabb"]).reshape(2, 3), dtype=torch.float32)
-    m = NVFi(cfg, "cpu", aabb, [int(g) for g in meta["gridSize"]], [float(meta["near"]), float(meta["far"])])
-    own = m.state_dict()
-    for k in g2.files:
-        if k.startswith("D:sd:") and k[5:] in own:
-            own[k[5:]].copy_(torch.from_numpy(np.ascontiguousarray(g2[k])))
-    return m.to("cuda")
 
 
 def grads_of(model):

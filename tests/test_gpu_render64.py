@@ -2,7 +2,7 @@
 compacted lists and the whole backward) against its float64 restatement (tests/render64.py, pinned to the reference's goldens by
 tests/test_render64_golden.py), on the device's own appearance mask where the call returns its weight map.
 
-Cases (tests/render64_worker.py):
+Cases (tests/render64_worker.py; the SH-shaded cases and their bound table follow the MLP ones further down):
   head_nonkey / head_key / head_extrap   the bench field (199^3, K = 16, 128 samples per ray), 2048 rays of the bench camera bundle through
         render_mse_backward_ - the calls bench.py times - at one RK2 step, at a keyframe (no warp, the keyframe fork of the backward) and past the
         last keyframe (four RK2 steps, asserted through last_counters[3] = list x 2 x steps); head_autograd: the same rays through forward() +
@@ -63,7 +63,64 @@ processes; the float64 references run on the GPU).
 Two mutations that only skip work, each built and run once: k_app_bwd's last partial workgroup returning early failed 32 of the 35 tests here (all
 but m0, m128, m32768, where no partial workgroup exists) and 11 older ones (test_render_train_grads, test_render_vs_oracle_bigger,
 test_fullsize_slice_matches_oracle, test_gpu_cfg1_matches_reference, the x6 backward check); k_wgrad_ring8 not contracting its last tile failed 28
-here (all but the single-tile lists and head_extrap / r8192, whose last tile holds one sample) and 8 older ones."""
+here (all but the single-tile lists and head_extrap / r8192, whose last tile holds one sample) and 8 older ones.
+
+SH shading (shadingMode "SH": k_app_fwd stops after basis_mat and writes relu(sum_k SH_k(view) feat[9c + k] + 0.5) from the lane pair (l, l + 32),
+k_app_bwd seeds its tile from w g_rgb gated by the stored colour and by the pre-clamp test 0 <= rgb_pre <= 1, the weight-gradient ring has the
+single basis_mat job, the six render-MLP slots of the gradient struct are empty).  Scenes D (helpers.sh_model: field A's 20 x 18 x 16 grid, 59
+samples per ray, K = 4, tmax = 0.75) and Dclamp (basis_mat.weight x 12).  Cases:
+  shD_nonkey / shD_key / shD_extrap: the 256 golden rays through forward() + backward() with the golden-style loss at t = 19/60, t = 0.25 (a
+        keyframe: the forked backward) and t = 0.95 (past tmax: two RK2 steps, asserted through last_counters[3]); shD_fused_nonkey / _key: the same
+        rays through render_mse_backward_ - the fused driver with empty MLP slots.  It needed no change: it passes None through to the library.
+  shm<N>, N = 1, 31, 32, 33, 127, 128, 129, 32768, 32769 and shr<N>, N = 1, 3, 4, 5: as m<N> / r<N>, from the pool of field A's golden rays under six
+        jitter draws and 768 grazing rays (1372 rays in the two largest).  Every one asserts its counter.
+  shclamp / shclamp_fused: Dclamp, 256 rays, white background, both drivers.  From the yardstick alone (test_sh_clamp_case_takes_both_kinks): 24.7 %
+        of the 768 channels sit at the upper clamp, 19.7 % of the 21 240 masked (sample, channel) colours are dead, 0 of the 256 pool rays seen had
+        to be passed over (smallest margin: 5.5 x the rounding bound at a sample's ReLU, 1080 x at a ray's clamp), and cutting the loss terms of
+        the clamped channels moves basis_mat and the appearance planes by 2e-15 (cutting the others: by 100 %).
+  Switches, one process each, on shD_nonkey, shD_key, shm129, shm32769: NVFI_FUSED_LAUNCH=0, NVFI_BWD_FORK=0, NVFI_SCATTER=lds,
+        NVFI_SCATTER_TILES=0, NVFI_DETERMINISTIC=1; all agree with the defaults to two digits (shm32769 app 8.4e-7 - 1.2e-6).
+  Every case also runs the yardstick's wrong variant (basis 6 with zz - xx - yy) under the same mask; where more than 32 samples are masked its
+  basis_mat / appearance-plane gradients have to leave the case's bound (they move by 2e-2 (shm33) to 3.7e-1; rgb by 8.6e-6 (shm33) to 3.2e-1).
+Bounds of the SH cases, same derivation, same format - B [float32 figure] / device; tile shifts as above (small cases: last masked sample app / mlp):
+  case               density                  app                      mlp (basis_mat)          vel                     tile: app / mlp / RK2 vel
+  shD_nonkey         1e-5 [2.1e-6] / 1.6e-6   1e-5 [1.4e-6] / 5.8e-7   1e-5 [3.5e-7] / 1.9e-7   1e-5 [8.9e-7] / 6.9e-7  1.5e-1 / 4.0e-2 / 2.9e-2
+  shD_key            1e-5 [1.5e-6] / 6.6e-7   1e-5 [1.2e-6] / 6.5e-7   1e-5 [3.6e-7] / 1.3e-7   -                       2.0e-1 / 4.1e-2
+  shD_extrap         1e-5 [2.6e-6] / 3.0e-6   1e-5 [8.8e-7] / 8.1e-7   1e-5 [2.4e-7] / 2.5e-7   1e-5 [8.9e-7] / 7.3e-7  4.3e-2 / 1.4e-2 / 4.6e-2
+  shD_fused_nonkey   1e-5 [2.3e-6] / 5.8e-7   1e-5 [1.4e-6] / 5.6e-7   1e-5 [3.5e-7] / 1.9e-7   1e-5 [3.4e-7] / 3.9e-7  1.5e-1 / 4.0e-2 / 1.1e-3
+  shD_fused_key      1e-5 [1.7e-6] / 5.7e-7   1e-5 [1.2e-6] / 7.2e-7   1e-5 [3.6e-7] / 1.3e-7   -                       2.0e-1 / 4.1e-2
+  shm32768           1e-5 [1.1e-6] / 1.0e-6   1e-5 [1.1e-6] / 8.5e-7   1e-5 [3.3e-7] / 8.0e-7   1e-5 [2.2e-7] / 3.7e-7  3.5e-2 / 8.3e-3 / 3.6e-3
+  shm32769           1e-5 [1.1e-6] / 1.0e-6   1e-5 [1.1e-6] / 8.4e-7   1e-5 [3.3e-7] / 8.1e-7   1e-5 [2.2e-7] / 3.5e-7  3.5e-2 / 8.3e-3 / 3.5e-3
+  shclamp            1e-5 [2.4e-6] / 1.3e-6   1e-5 [1.3e-6] / 4.5e-7   1e-5 [2.2e-7] / 2.7e-7   1e-5 [1.0e-6] / 5.6e-7  1.1e-1 / 4.4e-2 / 2.4e-2
+  shclamp_fused      1e-5 [2.1e-6] / 1.3e-6   1e-5 [1.3e-6] / 4.5e-7   1e-5 [2.2e-7] / 2.7e-7   1e-5 [8.1e-7] / 6.5e-7  1.1e-1 / 4.4e-2 / 3.1e-2
+  shm1               1e-5 [8.4e-7] / 8.4e-7   4e-4 [1.1e-4] / 1.1e-4   4e-4 [1.0e-4] / 1.1e-4   -                       1.0 / 1.0
+  shm31, 32, 33      1e-5 [1.3e-6] / 1.3e-6   3e-4 [7.0e-5] / 7.0e-5   6e-5 [1.9e-5] / 2.8e-5   1e-4 [3.7e-6] / 6.8e-6  8.3e-2 / 2.0e-2
+  shm127             2e-5 [5.4e-6] / 5.1e-6   1e-5 [9.2e-7] / 9.6e-7   1e-5 [4.5e-7] / 1.1e-6   2e-5 [3.5e-6] / 2.8e-6  9.9e-4 / 3.1e-4
+  shm128, shm129, shr<N>: B_SMALL = 1e-5 in every family; float32 at most 1.9e-6 / 2.0e-6 / 9.0e-7 / 1.1e-6, device at most 7.5e-6 (shm128,
+  density_plane_space.0) / 2.2e-6 / 1.2e-6 / 1.6e-6; the last masked sample moves app / mlp by at least 3.4e-4 / 1.3e-4.
+  Every large SH case fits under 1e-5: three times its float32 figure is at most 7.8e-6, and a third of a lost tile is never under 2.8e-3.
+  Where the float32 figure is large it is the case: the selections of 1 - 33 masked samples are grazing rays whose weights lie just over the
+  appearance threshold of 1e-4.  alpha = 1 - exp(-sigma dist) of such a sample carries the cancellation of two numbers near 1: 6e-8 absolute (far
+  inside FP32_FLOOR on the maps) is 1e-4 of the weight, and an SH colour's gradient is w g_rgb SH_k - linear in that weight, with no second
+  sample to average over in shm1.  The plain float32 evaluation and the device show the same figure to two digits, on the same tensor.  The MLP
+  cases never meet this: field B's density floor masks every valid sample, at weights far over the threshold.
+  The velocity bound of shm31 - shm33 is not 3 x 3.7e-6: below 3.1e-5 the float32 evaluation itself leaves 5 % of vel_net.weight_net.7.0.weight
+  outside assert_grad's element-wise check (shm33; one of the net's six output rows nearly cancels over 28 samples, and an error that is 4e-6
+  of the tensor's peak is 2e-3 of such a row); the bound is 3 x that 3.1e-5, rounded up.  The device passes from 9.8e-5 on (shm32, same tensor,
+  same row; its metric there is 6.8e-6) - the x6 adjoint of the velocity net adds in another order than torch's blocked sums.
+  shm129 cannot see its last valid sample in the density branch (the sample lies behind an opaque stretch, the move is 6e-11): BLIND, asserted.
+Two mutations of the SH path that change one value select each, built apart and run once against the SH cases and the older tests that reach
+SH code (test_sh_mode, test_gpu_lookup, test_gpu_pointshade, test_gpu_point64: 180 tests):
+  (a) k_app_bwd's SH block passing the gradient where rgb_pre > 1: failed shclamp and shclamp_fused (app_plane_space.0 off by 225 %) and nothing
+      else - none of the 180 older tests, none of the other 25 SH tests here.
+  (b) k_app_fwd's SH epilogue leaving the partner lane's partial sum out of the last partial tile: failed 21 of the 27 SH tests here - every
+      case but shm32, shm128, shm32768 (no partial tile) and the two yardstick-only clamp tests.  Of the older tests it failed 16 of the
+      point tests on field D (k_app_fwd is the point queries' kernel too: test_app_at_and_render_mlp, test_raw_against_yardstick, test_lookup_rgb,
+      test_prefix_invariance) and test_sh_mode - not at its 5e-4 on the gradients but on the eval rgb map, 2 of 256 rays outside 1e-4 where 1
+      is allowed.  So the render call's SH forward was not without a net; its backward's clamp branch (a) was.
+No defect of the library was found: the fused driver with empty slots, the early return of the SH forward, the 27-of-32-row basis_mat job at
+NSLAB + 1 samples and the deterministic scatter all sit at the float32 figures above.  The SH cases add 27 s to the file (27 tests, six worker
+processes of 3.5 - 6 s): 78 s for its 62 tests in one run on an MI355X, of which the parent's 35 tests take 49 s."""
 import hashlib
 import os
 import subprocess
@@ -88,16 +145,30 @@ B_GROUP = {"head_autograd": "head_nonkey", "m0": "head_nonkey", "r8193": "r8192"
 B_SMALL = 1e-5        # the field-B cases of at most a few hundred samples, and big_preact
 # large cases whose list is too long for the bound to see one lost tile of it (the yardstick's move is under 3 x the bound): said here, and
 # asserted to BE blind so that the entry cannot outlive its reason; the 128 x 256 + 1 case and the k<N> cases carry those lists
-BLIND = {("big686", "last RK2 tile")}
+BLIND = {("big686", "last RK2 tile"),
+         ("shm129", "last valid sample")}     # the last valid sample of its last ray lies behind an opaque stretch: T = 6e-11 there
 
 
 def _bounds(case):
     g = B_GROUP.get(case, case)
     return dict(zip(_F, B_R[g])) if g in B_R else dict.fromkeys(_F, B_SMALL)
+
+
+# ---- SH shading (scene D / Dclamp of the worker): the docstring's second table
+SH_MAIN = ["shD_nonkey", "shD_key", "shD_extrap", "shD_fused_nonkey", "shD_fused_key"]
+SH_SMALL = [f"shm{n}" for n in (1, 31, 32, 33, 127, 128, 129)] + [f"shr{n}" for n in (1, 3, 4, 5)]
+SH_LARGE = ["shm32768", "shm32769", "shclamp", "shclamp_fused"]
+SH_SWITCH_CASES = ["shD_nonkey", "shD_key", "shm129", "shm32769"]
+SH_SWITCHES = ["unfused_launch", "no_fork", "scatter_lds", "scatter_atomic", "deterministic"]      # the velocity-kernel switches do not depend on the shading
+# the SH cases whose float32 figure does not fit under B_SMALL (the docstring says why): 3 x the figure, rounded up, in those families only
+B_R.update({"shm1": (1e-5, 4e-4, 4e-4, 1e-5), "shm31": (1e-5, 3e-4, 6e-5, 1e-4), "shm127": (2e-5, 1e-5, 1e-5, 2e-5)})
+B_GROUP.update({"shm32": "shm31", "shm33": "shm31"})
+SH_WORKER_LIMIT = 120          # seconds; the default worker takes about 6 s, a switch worker 3.5 s
 MAP_RTOL = 5e-5
 LOSS_RTOL = 3e-6
 HEAD = ["head_nonkey", "head_key", "head_autograd", "head_extrap"]
-SMALL = ["m0", "m1", "m31", "m32", "m33", "m127", "m128", "m129", "k1", "k33", "k129", "k160", "r1", "r3", "r4", "r5"]
+SMALL_MLP = ["m0", "m1", "m31", "m32", "m33", "m127", "m128", "m129", "k1", "k33", "k129", "k160", "r1", "r3", "r4", "r5"]
+SMALL = SMALL_MLP + SH_SMALL
 LARGE = ["m32768", "m32769", "r2049", "r8192", "r8193", "big686", "big_preact"]
 SWITCH_CASES = ["head_nonkey", "head_key", "m129", "m32769"]
 SWITCHES = {"fp32_adjoint": dict(NVFI_FUSE_X6="0"), "rk2_unfused": dict(NVFI_RK2_FUSE="0"), "rk2_fp32": dict(NVFI_RK2_X6="0"),
@@ -108,7 +179,7 @@ _runs, _failed, _refs, _fields = {}, [], {}, {}
 _T0 = time.time()
 
 
-def _worker(tag, cases, env):
+def _worker(tag, cases, env, limit=600):
     """one worker process per switch setting; after a failed one no further worker is started"""
     if tag in _runs:
         return _runs[tag]
@@ -118,7 +189,7 @@ def _worker(tag, cases, env):
     _failed.append(tag)          # taken back only when the worker's results are in: a time limit, a crash or an unreadable file all stop the file here
     try:
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "render64_worker.py"), out, ",".join(cases)],
-                           env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+                           env=dict(os.environ, **env), capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired as e:
         pytest.fail(f"worker {tag} ran into its time limit:\n" + str(e.stdout)[-2000:] + str(e.stderr)[-3000:])
     if r.returncode != 0:
@@ -132,7 +203,11 @@ def _worker(tag, cases, env):
 
 
 def _defaults():
-    return _worker("defaults", HEAD + SMALL + LARGE, {})
+    return _worker("defaults", HEAD + SMALL_MLP + LARGE, {})
+
+
+def _defaults_sh():
+    return _worker("sh_defaults", SH_MAIN + SH_SMALL + SH_LARGE, {}, SH_WORKER_LIMIT)
 
 
 def _device():
@@ -182,7 +257,7 @@ def _metric(a, b):
 def _shift(ref, cut):
     """per family, the largest move of a tensor of the yardstick relative to its bound"""
     out = {}
-    for n in r64.NAMES:
+    for n in cut:
         if cut[n] is not None and np.abs(ref["grads"][n]).max() > 0:
             f = r64.FAMILY[n]
             out[f] = max(out.get(f, 0.0), _metric(cut[n], ref["grads"][n]))
@@ -208,7 +283,9 @@ def _check(z, case, label):
             # the worst case grows with the number of factors, so a 686-sample ray gets 686 / 128 of it)
             maps[m] = (float(err.max()), float((err - FP32_FLOOR[m] * max(1.0, fld.S / 128.0) - MAP_RTOL * np.abs(ref[m])).max()))
     lerr = abs(float(z[f"{case}:loss"]) - ref["loss"]) / abs(ref["loss"])
-    errs = {n: _metric(z[f"{case}:g:{n}"], ref["grads"][n]) for n in r64.NAMES
+    names = fld.names
+    base = case[2:] if case.startswith("sh") else case          # shm<N> / shr<N> carry the counters of m<N> / r<N>
+    errs = {n: _metric(z[f"{case}:g:{n}"], ref["grads"][n]) for n in names
             if ref["grads"][n] is not None and f"{case}:g:{n}" in z and np.abs(ref["grads"][n]).max() > 0}
     fam = {}
     for n, e in errs.items():
@@ -230,18 +307,29 @@ def _check(z, case, label):
         if nsteps:
             t0 = (len(ig) // 32 - 1) * 32
             sens["last RK2 tile"] = (_shift(ref, r64.detach(ref, ig[t0:t0 + 32], "warp")), ("vel",), 3.0)
+    wrong_rgb = None
+    if fld.sh and masked > 32:
+        # the yardstick's wrong variant (basis 6 with zz - xx - yy) under the same mask: the bounds of this case have to see it
+        c = ref["call"]
+        full = np.zeros((ref["R"], ref["app_mask"].shape[1]), bool)
+        full[ref["rays"]] = ref["app_mask"]
+        wr = r64.render64(fld, c["rays_o"], c["rays_d"], c["t"], c["jitter"], c["white_bg"], app_mask=full, loss=c["loss"], device=c["device"], wrong=True)
+        sens["wrong basis"] = (_shift(ref, wr["grads"]), ("mlp", "app"), 1.0)
+        werr = np.abs(wr["rgb"] - ref["rgb"])
+        wrong_rgb = (float(werr.max()), float((werr - FP32_FLOOR["rgb"] - MAP_RTOL * np.abs(ref["rgb"])).max()))
     print(f"[render64] {label}: R {R}, counters {cnt[:4].tolist()}, yardstick valid {int(ref['valid'].sum())} gate {int(ref['in_gate'].sum())} masked "
           f"{masked}, RK2 steps {nsteps}; mask flips {flips} on {flip_rays} rays" + (f" (max |w64 - thres| {fdist.max():.2e})" if flips else "")
           + f"; loss rel err {lerr:.2e}; maps (max abs err, excess over the bound) {maps}; gradient err per family "
           + ", ".join(f"{f} {e:.2e} ({n})" for f, (e, n) in sorted(fam.items()))
-          + "; shifts " + ", ".join(f"{k}: " + " ".join(f"{f} {v:.2e}" for f, v in sorted(s.items())) for k, (s, _, _) in sens.items()), flush=True)
+          + "; shifts " + ", ".join(f"{k}: " + " ".join(f"{f} {v:.2e}" for f, v in sorted(s.items())) for k, (s, _, _) in sens.items())
+          + (f"; the wrong basis moves rgb by {wrong_rgb[0]:.2e}" if wrong_rgb else ""), flush=True)
     # ---- the counters
-    if case[0] == "m" and case[1:].isdigit():
-        assert int(cnt[2]) == int(case[1:]), (label, "masked count", int(cnt[2]))
-    if case[0] == "k" and case[1:].isdigit():
-        assert int(cnt[1]) == int(case[1:]), (label, "RK2 list", int(cnt[1]))
-    if case[0] == "r" and case[1:].isdigit():
-        assert R == int(case[1:])
+    if base[0] == "m" and base[1:].isdigit():
+        assert int(cnt[2]) == int(base[1:]), (label, "masked count", int(cnt[2]))
+    if base[0] == "k" and base[1:].isdigit():
+        assert int(cnt[1]) == int(base[1:]), (label, "RK2 list", int(cnt[1]))
+    if base[0] == "r" and base[1:].isdigit():
+        assert R == int(base[1:])
     if case == "m0":
         assert int(cnt[0]) > 0, (label, "valid samples present")
     assert int(cnt[0]) == int(ref["valid"].sum()), (label, "valid count", int(cnt[0]), int(ref["valid"].sum()))
@@ -251,6 +339,12 @@ def _check(z, case, label):
         assert nsteps >= 3 and int(cnt[1]) > 0, (label, nsteps)
     if case == "head_key":
         assert nsteps == 0
+    if case == "shD_extrap":
+        assert nsteps >= 2 and int(cnt[1]) > 0, (label, nsteps)
+    if case in ("shD_key", "shD_fused_key"):
+        assert nsteps == 0
+    if case in ("shD_nonkey", "shD_fused_nonkey") or case.startswith(("shm", "shr", "shclamp")):
+        assert nsteps == 1
     # ---- the masks
     if f"{case}:weights" in z:
         assert int(cnt[2]) == masked, (label, int(cnt[2]), masked)
@@ -265,7 +359,9 @@ def _check(z, case, label):
         assert excess <= 0, (label, m, "max abs err", emax)
     assert lerr <= LOSS_RTOL, (label, "loss", lerr)
     # ---- the gradients
-    for n in r64.NAMES:
+    if fld.sh:
+        assert not any(f"{case}:g:{n}" in z for n in r64.MLP_NAMES), (label, "an SH field has no render-MLP gradient")
+    for n in names:
         g = z.get(f"{case}:g:{n}")
         if ref["grads"][n] is None or np.abs(ref["grads"][n]).max() == 0:
             assert g is None or not np.any(g), (label, n, "no term of the loss reaches it")
@@ -283,9 +379,60 @@ def _check(z, case, label):
     return fam
 
 
-@pytest.mark.parametrize("case", HEAD + SMALL + LARGE)
+@pytest.mark.parametrize("case", HEAD + SMALL_MLP + LARGE)
 def test_render_matches_float64(case):
     _check(_defaults(), case, f"defaults:{case}")
+
+
+@pytest.mark.parametrize("case", SH_MAIN + SH_SMALL + SH_LARGE)
+def test_sh_render_matches_float64(case):
+    _check(_defaults_sh(), case, f"sh_defaults:{case}")
+
+
+@pytest.mark.parametrize("case", ["shclamp", "shclamp_fused"])
+def test_sh_clamp_case_takes_both_kinks(case):
+    """what shclamp is for, asserted from the yardstick alone (under the device's mask): enough channels at the upper clamp, enough dead sample
+    colours, no kink nearer than 4 x its rounding bound, few pool rays passed over - and a clamped channel gives basis_mat and the appearance
+    planes nothing: with the loss terms of those channels cut, their gradients do not change (with the others cut they do)"""
+    z = _defaults_sh()
+    ref, fld = _reference(z, case)
+    c = ref["call"]
+    mask = ref["app_mask"]
+    m = r64.render64(fld, c["rays_o"], c["rays_d"], c["t"], c["jitter"], True, app_mask=mask, loss=None, grads=False, device=c["device"], want_margin=True)
+    clamped = ref["rgb"] >= 1.0
+    share_c, share_d = float(clamped.mean()), float(m["dead"].sum() / (3.0 * mask.sum()))
+    redrawn, seen = int(z[f"{case}:redrawn"]), int(z[f"{case}:pool_seen"])
+    app = [n for n in fld.names if n.startswith("app") or n == "basis_mat.weight"]
+    tg, gw = z[f"{case}:target"], z.get(f"{case}:gw")
+    mk = (lambda keep: r64.Loss(tg, keep=keep)) if gw is None else (lambda keep: r64.Loss(tg, 0.01, 0.02, gw, keep=keep))
+    kw = dict(app_mask=mask, device=c["device"])
+    cut = r64.render64(fld, c["rays_o"], c["rays_d"], c["t"], c["jitter"], True, loss=mk(~clamped), **kw)["grads"]
+    rest = r64.render64(fld, c["rays_o"], c["rays_d"], c["t"], c["jitter"], True, loss=mk(clamped), **kw)["grads"]
+    d_cut = max(_metric(cut[n], ref["grads"][n]) for n in app)
+    d_rest = min(_metric(rest[n], ref["grads"][n]) for n in app)
+    print(f"[render64] {case}: {share_c:.1%} of the {clamped.size} channels at the upper clamp, {share_d:.1%} of the {3 * int(mask.sum())} masked "
+          f"(sample, channel) colours dead, {redrawn} of {seen} pool rays passed over; smallest margin sample {m['margin'][mask].min():.1f}, ray "
+          f"{m['margin_ray'].min():.1f}; appearance-side gradients move by {d_cut:.1e} with the clamped channels' loss terms cut, by at least "
+          f"{d_rest:.1e} with the others cut")
+    assert 0.10 <= share_c <= 0.60, share_c
+    assert 0.05 <= share_d <= 0.95, share_d
+    assert redrawn <= 0.02 * seen, (redrawn, seen)
+    assert m["margin"][mask].min() > 4.0 and m["margin_ray"].min() > 4.0
+    assert d_cut <= 1e-13 and d_rest > 1e-2, (d_cut, d_rest)
+
+
+@pytest.mark.parametrize("setting", SH_SWITCHES)
+def test_sh_render_switch_matches_float64(setting):
+    z = _worker("sh_" + setting, SH_SWITCH_CASES, SWITCHES[setting], SH_WORKER_LIMIT)
+    bad = []
+    for case in SH_SWITCH_CASES:
+        assert bool(z[f"{case}:fork"]) == (setting != "no_fork"), (setting, "field.fork_backward")
+        try:
+            _check(z, case, f"{setting}:{case}")
+        except AssertionError as e:
+            bad.append(f"{case}: {e}")
+    print(f"[render64] wall time of the file up to sh:{setting}: {time.time() - _T0:.0f} s")
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("setting", list(SWITCHES))

@@ -143,3 +143,119 @@ def test_render64_sums_over_rays_and_cuts(gold, fields64):
     assert max(moved[n] for n in r64.MLP_NAMES) > 0 and max(moved[n] for n in r64.NAMES if n.startswith("density")) < 1e-12, moved
     cut = r64.detach(full, np.argwhere(full["valid"])[-1:], "sigma")
     assert maxrel(cut["density_plane_space.0"], full["grads"]["density_plane_space.0"]) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- field D: SH shading
+# tests/golden/r2.npz, field D = field A's geometry with shadingMode "SH" (make_golden_r2.py): two eval renders (rgb, depth, acc; no weight map
+# is stored) and one train render at t = 19/60 with the loss mse + 0.01 mean(depth) and its 25 gradient tensors.  Same rules and bounds as A and B.
+# Measured (CPU): float64 against the fp32 goldens: gradients 1.8e-6 worst (density_plane_time.2), loss rel err 3.8e-8, maps max abs err rgb 2.6e-7,
+# acc 4.7e-7, depth 2.2e-6.  render64 in float32 against itself in float64 on D:train, per family (the floor of the SH bounds of
+# tests/test_gpu_render64.py; asserted to fit three times under GRAD_BOUND): density 1.9e-6, app 1.1e-6, mlp (basis_mat) 3.4e-7, vel 2.7e-7; the
+# masks agree on all 7 067 - 7 104 masked samples.  The wrong variant (basis 6 with zz - xx - yy) moves rgb by 2.9e-2 and takes all 25 gradient
+# tensors out of the bound (basis_mat.weight by 2.3e-1).  No masked colour of D:train lies within 4 x its rounding bound of a kink (relu_margin).
+@pytest.fixture(scope="module")
+def field_d():
+    import os
+    from conftest import GOLD
+    g2 = np.load(os.path.join(GOLD, "r2.npz"))
+    meta, _ = load_meta("A")
+    sd = {k[len("D:sd:"):]: g2[k] for k in g2.files if k.startswith("D:sd:")}
+    f = r64.Field(sd, meta)
+    assert f.sh and f.names == r64.SH_NAMES and not any(n in f.p32 for n in r64.MLP_NAMES)
+    return f, g2
+
+
+def _maps_d(r, g2, pre, label):
+    for m in ("rgb", "depth", "acc"):
+        if pre + m not in g2.files:
+            continue
+        ref = g2[pre + m].astype(np.float64)
+        err = np.abs(r[m] - ref)
+        print(f"[render64] {label}:{m}: max abs err {err.max():.2e}")
+        assert (err <= MAP_RTOL * np.abs(ref) + FP32_FLOOR[m]).all(), (label, m, float(err.max()))
+
+
+@pytest.mark.parametrize("name,t", [("nonkey", 19.0 / 60.0), ("key", 0.25)])
+def test_render64_sh_matches_the_reference_eval_goldens(gold, field_d, name, t):
+    f, g2 = field_d
+    o, d = gold["A:rays_o"], gold["A:rays_d"]
+    kw = dict(loss=None, grads=False)
+    r = r64.render64(f, o, d, t, None, True, **kw)
+    r32 = r64.render64(f, o, d, t, None, True, dtype=torch.float32, **kw)
+    assert len(r["plan"]["steps"]) == (1 if name == "nonkey" else 0)
+    _mask_condition(r, r32, f.thres, f"D:render_{name}:")
+    _maps_d(r, g2, f"D:render_{name}:", f"D:render_{name}")
+    bad = r64.render64(f, o, d, t, None, True, wrong=True, **kw)
+    err = np.abs(bad["rgb"] - g2[f"D:render_{name}:rgb"])
+    print(f"[render64] D:render_{name}: the wrong basis moves rgb by {err.max():.2e}")
+    assert (err > MAP_RTOL * np.abs(g2[f"D:render_{name}:rgb"]) + FP32_FLOOR["rgb"]).any()
+
+
+def test_render64_sh_matches_the_reference_train_golden(gold, field_d):
+    f, g2 = field_d
+    o, d = gold["A:rays_o"], gold["A:rays_d"]
+    loss = r64.Loss(g2["D:train:target"], 0.01)          # make_golden_r2.py: mse + 0.01 mean(depth)
+    kw = dict(loss=loss)
+    r = r64.render64(f, o, d, 19.0 / 60.0, g2["D:train:u"], True, **kw)
+    r32 = r64.render64(f, o, d, 19.0 / 60.0, g2["D:train:u"], True, dtype=torch.float32, **kw)
+    bad = r64.render64(f, o, d, 19.0 / 60.0, g2["D:train:u"], True, wrong=True, **kw)
+    assert len(r["plan"]["steps"]) == 1 and r["app_mask"].sum() > 5000 and r["flips"].size == 0
+    assert set(r["grads"]) == set(r64.SH_NAMES)
+    _mask_condition(r, r32, f.thres, "D:train:")
+    _maps_d(r, g2, "D:train:", "D:train")
+    for m in ("rgb", "depth", "acc", "weight"):
+        print(f"[render64] D:train:{m}: float32 evaluation against float64 max abs {np.abs(r32[m] - r[m]).max():.2e}")
+    gl = float(g2["D:train:loss"].reshape(-1)[0])
+    lerr = abs(r["loss"] - gl) / abs(gl)
+    gp = "D:train:grad:nvfi."
+    checked, worst, fam32, seen, out = 0, (0.0, None), {}, [], []
+    for k in g2.files:
+        if not k.startswith(gp):
+            continue
+        pn, ref = k[len(gp):], g2[k]
+        got = r["grads"][pn]
+        e = max(maxrel(got, ref), rel_l2(got, ref))
+        worst = max(worst, (e, pn))
+        fm = r64.FAMILY[pn]
+        fam32[fm] = max(fam32.get(fm, 0.0), max(maxrel(r32["grads"][pn], got), rel_l2(r32["grads"][pn], got)))
+        if max(maxrel(bad["grads"][pn], ref), rel_l2(bad["grads"][pn], ref)) > GRAD_BOUND:
+            seen.append(pn)
+        if not e <= GRAD_BOUND:
+            out.append((pn, e))
+        checked += 1
+    print(f"[render64] D:train: loss rel err {lerr:.2e}; {checked} gradient tensors, worst against the golden {worst[0]:.2e} ({worst[1]}); float32 "
+          "evaluation against float64 per family " + ", ".join(f"{k} {v:.2e}" for k, v in sorted(fam32.items()))
+          + f"; the wrong basis leaves the bound on {len(seen)} tensors (basis_mat.weight "
+          f"{max(maxrel(bad['grads']['basis_mat.weight'], g2[gp + 'basis_mat.weight']), rel_l2(bad['grads']['basis_mat.weight'], g2[gp + 'basis_mat.weight'])):.2e}), "
+          f"rgb by {np.abs(bad['rgb'] - g2['D:train:rgb']).max():.2e}")
+    assert lerr <= LOSS_RTOL, lerr
+    assert not out, out
+    assert checked == 25, checked
+    assert all(3 * v <= GRAD_BOUND for v in fam32.values()), fam32
+    # the wrong variant is seen: on the map and on basis_mat and the appearance planes
+    err = np.abs(bad["rgb"] - g2["D:train:rgb"])
+    assert (err > MAP_RTOL * np.abs(g2["D:train:rgb"]) + FP32_FLOOR["rgb"]).any()
+    assert "basis_mat.weight" in seen and any(n.startswith("app_plane") for n in seen), seen
+
+
+def test_render64_sh_bookkeeping(gold, field_d):
+    """with_mask and detach on an SH field (no render-MLP names anywhere), and relu_margin's SH form: finite exactly on the masked samples"""
+    f, g2 = field_d
+    o, d, u = gold["A:rays_o"], gold["A:rays_d"], g2["D:train:u"]
+    loss = r64.Loss(g2["D:train:target"], 0.01)
+    full = r64.render64(f, o, d, 19.0 / 60.0, u, True, loss=loss)
+    mask = full["app_mask"].copy()
+    ij = r64.list_order(mask)
+    mask[ij[7][0], ij[7][1]] = False
+    upd = r64.with_mask(full, mask)
+    again = r64.render64(f, o, d, 19.0 / 60.0, u, True, loss=loss, app_mask=mask)
+    for n in f.names:
+        np.testing.assert_allclose(upd["grads"][n], again["grads"][n], rtol=1e-8, atol=1e-12 * np.abs(again["grads"][n]).max())
+    cut = r64.detach(full, ij[-1:], "rgb")
+    moved = {n: maxrel(cut[n], full["grads"][n]) for n in f.names}
+    assert moved["basis_mat.weight"] > 0 and max(moved[n] for n in f.names if n.startswith("density")) < 1e-12, moved
+    ms, mr = r64.relu_margin(f, o, d, 19.0 / 60.0, u)
+    assert ms.shape == full["app_mask"].shape + (3,) and mr.shape == (o.shape[0], 3)
+    assert (np.isfinite(ms).all(-1) == full["app_mask"]).all() and (ms[full["app_mask"]] > 0).all()
+    print(f"[render64] D:train: masked (sample, channel) colours within 4 x their rounding bound of the ReLU kink: {int((ms < 4).sum())} of "
+          f"{3 * int(full['app_mask'].sum())}; (ray, channel) within 4 x of a clamp kink: {int((mr < 4).sum())} of {mr.size}")
