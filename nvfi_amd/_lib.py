@@ -62,25 +62,89 @@ class DrawDesc(C.Structure):
                 ("P", C.c_int64), ("aabb", C.c_float * 6), ("points", fp), ("t", fp)]
 
 
-EXPORTS = [
-    "nvfi_last_error", "nvfi_abi_version",
-    "nvfi_render_workspace_bytes", "nvfi_render_workspace_bytes_t", "nvfi_render_fwd", "nvfi_render_bwd", "nvfi_render_fwd_t", "nvfi_render_bwd_t",
-    "nvfi_pde_loss_dev", "nvfi_adam_step_dev", "nvfi_frag_cache_bytes", "nvfi_pack_frags", "nvfi_stream_capture_id", "nvfi_render_fwd_mse", "nvfi_draw_batch",
-    "nvfi_pde_workspace_bytes", "nvfi_pde_loss", "nvfi_pde_loss_ex", "nvfi_pde_loss_split", "nvfi_plane_regs", "nvfi_plane_regs_dev", "nvfi_adam_step", "nvfi_mse", "nvfi_render_mask", "nvfi_render_export_masked", "nvfi_maskfield_workspace_bytes", "nvfi_maskfield_fwd", "nvfi_maskfield_bwd", "nvfi_sh_render", "nvfi_compute_alpha", "nvfi_gen_rays",
-    "nvfi_vel_eval", "nvfi_vel_workspace_bytes", "nvfi_integrate_pos", "nvfi_density_at", "nvfi_app_at", "nvfi_render_mlp", "nvfi_app_workspace_bytes", "nvfi_alpha_workspace_bytes",
-    "nvfi_comm_unique_id", "nvfi_comm_init", "nvfi_allreduce_grads", "nvfi_comm_destroy", "nvfi_selftest", "nvfi_debug_act", "nvfi_prof_enable", "nvfi_prof_collect", "nvfi_prof_nclasses",
-    "nvfi_segloss_workspace_bytes", "nvfi_knn_self", "nvfi_segloss",
-    "nvfi_metrics_workspace_bytes", "nvfi_ssim", "nvfi_segm_confusion",
-    "nvfi_render_flow", "nvfi_render_objects", "nvfi_render_fwd_select",
-    "nvfi_char_workspace_bytes", "nvfi_char_loss",
-    "nvfi_depth_loss",
-    "nvfi_advect_grad_workspace_bytes", "nvfi_advect_grad",
-    "nvfi_ray_distortion_workspace_bytes", "nvfi_ray_distortion",
-    "nvfi_flow_loss_workspace_bytes", "nvfi_flow_loss_fwd", "nvfi_flow_loss_bwd",
-    "nvfi_density_grad", "nvfi_appfeat_at", "nvfi_appfeat_grad",
-    "nvfi_render_mlp_grad_workspace_bytes", "nvfi_render_mlp_grad",
-    "nvfi_mask_loss_workspace_bytes", "nvfi_mask_loss_fwd", "nvfi_mask_loss_bwd",
-]
+# The prototypes of include/nvfi_hip.h, one row per function in the header's order: a letter per parameter - p any pointer (a struct by
+# reference, a device pointer, a stream, NULL), l int64_t, i int, f float.  lib() turns every row into argtypes, so a call site passes plain
+# Python numbers and a wrong kind is refused before the call is made; tests/test_abi_and_host.py holds the table against the header.
+ABI_VERSION = 5
+KINDS = {"p": C.c_void_p, "l": C.c_int64, "i": C.c_int, "f": C.c_float}
+SIGNATURES = {
+    "nvfi_last_error": "",      # returns const char*; every other function an int error code
+    "nvfi_abi_version": "",
+    "nvfi_render_workspace_bytes": "plip",
+    "nvfi_render_workspace_bytes_t": "plifp",
+    "nvfi_render_fwd": "plpppfippppplpp",
+    "nvfi_render_bwd": "plppfippppppplp",
+    "nvfi_render_fwd_t": "plpppfpippppplpp",
+    "nvfi_render_bwd_t": "plppfiippppppplp",
+    "nvfi_render_fwd_mse": "plpppfpippppplppfppp",
+    "nvfi_frag_cache_bytes": "pp",
+    "nvfi_pack_frags": "pplp",
+    "nvfi_stream_capture_id": "pp",
+    "nvfi_pde_workspace_bytes": "plp",
+    "nvfi_pde_loss": "plppfppplpp",
+    "nvfi_pde_loss_ex": "plppfppplppplpp",
+    "nvfi_pde_loss_split": "plppfppplppplppp",
+    "nvfi_pde_loss_dev": "plpppppplpp",
+    "nvfi_render_mask": "pplfippplp",
+    "nvfi_render_export_masked": "plfipllppp",
+    "nvfi_render_flow": "plppffippiifpppplp",
+    "nvfi_render_objects": "pplfippppplp",
+    "nvfi_render_fwd_select": "ppplpppfippppplpp",
+    "nvfi_maskfield_workspace_bytes": "plip",
+    "nvfi_maskfield_fwd": "plppiplp",
+    "nvfi_maskfield_bwd": "plppiplp",
+    "nvfi_segloss_workspace_bytes": "liip",
+    "nvfi_knn_self": "lpifppppplp",
+    "nvfi_segloss": "lipppipppifffffipppppplp",
+    "nvfi_char_workspace_bytes": "plp",
+    "nvfi_char_loss": "plpffpppplp",
+    "nvfi_sh_render": "lpppp",
+    "nvfi_plane_regs": "pfffppp",
+    "nvfi_plane_regs_dev": "ppppp",
+    "nvfi_mse": "pplppp",
+    "nvfi_depth_loss": "lpppifpppp",
+    "nvfi_ray_distortion_workspace_bytes": "lp",
+    "nvfi_ray_distortion": "lipffppppplp",
+    "nvfi_flow_loss_workspace_bytes": "plfflp",
+    "nvfi_flow_loss_fwd": "plppffippiifppiffpippppllplp",
+    "nvfi_flow_loss_bwd": "plffllpplp",
+    "nvfi_mask_loss_workspace_bytes": "ppllp",
+    "nvfi_mask_loss_fwd": "pplfipppiffpippppllplp",
+    "nvfi_mask_loss_bwd": "plillpplp",
+    "nvfi_adam_step": "piffflip",
+    "nvfi_adam_step_dev": "pifffpip",
+    "nvfi_vel_eval": "plppiplp",
+    "nvfi_vel_workspace_bytes": "plp",
+    "nvfi_integrate_pos": "plppppplp",
+    "nvfi_advect_grad_workspace_bytes": "plffp",
+    "nvfi_advect_grad": "plpffpppplp",
+    "nvfi_density_at": "plpppp",
+    "nvfi_app_workspace_bytes": "plp",
+    "nvfi_app_at": "plpppplp",
+    "nvfi_density_grad": "plppppp",
+    "nvfi_appfeat_at": "plppp",
+    "nvfi_appfeat_grad": "plppppp",
+    "nvfi_render_mlp": "plppppplp",
+    "nvfi_render_mlp_grad_workspace_bytes": "plp",
+    "nvfi_render_mlp_grad": "plppppppppplp",
+    "nvfi_comm_unique_id": "p",
+    "nvfi_comm_init": "piip",
+    "nvfi_allreduce_grads": "pplip",
+    "nvfi_comm_destroy": "p",
+    "nvfi_prof_enable": "i",
+    "nvfi_prof_collect": "pp",
+    "nvfi_prof_nclasses": "",
+    "nvfi_alpha_workspace_bytes": "plp",
+    "nvfi_compute_alpha": "plpfifipplp",
+    "nvfi_gen_rays": "piiflpppp",
+    "nvfi_draw_batch": "pp",
+    "nvfi_metrics_workspace_bytes": "iliiip",
+    "nvfi_ssim": "liiipppppfipplp",
+    "nvfi_segm_confusion": "lliippppppplp",
+    "nvfi_debug_act": "ilppp",
+    "nvfi_selftest": "pp",
+}
+EXPORTS = list(SIGNATURES)
 
 _LIB = None
 
@@ -97,36 +161,12 @@ def lib():
             raise NvfiError(f"{SO} is missing: build it with `python -m nvfi_amd.build` (needs hipcc). "
                             "There is no CPU fallback for the NVFi hot path.")
         L = C.CDLL(SO)
-        L.nvfi_last_error.restype = C.c_char_p
-        for name in EXPORTS:
-            getattr(L, name)  # raises AttributeError on a missing symbol
-        i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
-        L.nvfi_metrics_workspace_bytes.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, i64p]
-        L.nvfi_ssim.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, fp, i64p, fp, i64p, f32p, C.c_float, C.c_int, fp, fp, C.c_int64, fp]
-        L.nvfi_segm_confusion.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_render_flow.argtypes = [fp, C.c_int64, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_render_objects.argtypes = [fp, fp, C.c_int64, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_render_fwd_select.argtypes = [fp, fp, fp, C.c_int64, fp, fp, fp, C.c_float, C.c_int, fp, fp, fp, fp, fp, C.c_int64, fp, fp]
-        L.nvfi_char_workspace_bytes.argtypes = [fp, C.c_int64, i64p]
-        L.nvfi_char_loss.argtypes = [fp, C.c_int64, fp, C.c_float, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_depth_loss.argtypes = [C.c_int64, fp, fp, fp, C.c_int, C.c_float, fp, fp, fp, fp]
-        L.nvfi_advect_grad_workspace_bytes.argtypes = [fp, C.c_int64, C.c_float, C.c_float, i64p]
-        L.nvfi_advect_grad.argtypes = [fp, C.c_int64, fp, C.c_float, C.c_float, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_ray_distortion_workspace_bytes.argtypes = [C.c_int64, i64p]
-        L.nvfi_ray_distortion.argtypes = [C.c_int64, C.c_int, fp, C.c_float, C.c_float, fp, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_flow_loss_workspace_bytes.argtypes = [fp, C.c_int64, C.c_float, C.c_float, C.c_int64, i64p]
-        L.nvfi_flow_loss_fwd.argtypes = [fp, C.c_int64, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, C.c_int, C.c_int, C.c_float, fp, fp, C.c_int, C.c_float,
-                                         C.c_float, fp, C.c_int, fp, fp, fp, fp, C.c_int64, C.c_int64, fp, C.c_int64, fp]
-        L.nvfi_flow_loss_bwd.argtypes = [fp, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, fp, fp, C.c_int64, fp]
-        L.nvfi_density_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
-        L.nvfi_appfeat_at.argtypes = [fp, C.c_int64, fp, fp, fp]
-        L.nvfi_appfeat_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp]
-        L.nvfi_render_mlp_grad_workspace_bytes.argtypes = [fp, C.c_int64, i64p]
-        L.nvfi_render_mlp_grad.argtypes = [fp, C.c_int64, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int64, fp]
-        L.nvfi_mask_loss_workspace_bytes.argtypes = [fp, fp, C.c_int64, C.c_int64, i64p]
-        L.nvfi_mask_loss_fwd.argtypes = [fp, fp, C.c_int64, C.c_float, C.c_int, fp, fp, fp, C.c_int, C.c_float, C.c_float, fp, C.c_int, fp, fp, fp,
-                                         fp, C.c_int64, C.c_int64, fp, C.c_int64, fp]
-        L.nvfi_mask_loss_bwd.argtypes = [fp, C.c_int64, C.c_int, C.c_int64, C.c_int64, fp, fp, C.c_int64, fp]
+        for name, kinds in SIGNATURES.items():      # getattr raises AttributeError on a missing symbol
+            getattr(L, name).argtypes = [KINDS[k] for k in kinds]
+        L.nvfi_last_error.restype = C.c_char_p      # every other function returns int, ctypes' default
+        if L.nvfi_abi_version() != ABI_VERSION:
+            raise NvfiError(f"{SO} has ABI version {L.nvfi_abi_version()}, this binding is written for {ABI_VERSION}: rebuild it "
+                            "with `python -m nvfi_amd.build` (or unset NVFI_LIB)")
         _LIB = L
     return _LIB
 
@@ -146,7 +186,7 @@ def bytes_of(fn, *args):
 def capture_id(stream_handle):
     """id (> 0) of the hipGraph capture the stream takes part in, 0 when it is not capturing"""
     cid = C.c_uint64(0)
-    check(lib().nvfi_stream_capture_id(C.c_void_p(stream_handle), C.byref(cid)))
+    check(lib().nvfi_stream_capture_id(stream_handle, C.byref(cid)))
     return cid.value
 
 

@@ -39,13 +39,13 @@ class RcclComm:
             dist.broadcast_object_list(box, src=0)
             ident = (C.c_char * 128).from_buffer_copy(box[0])
         self.handle = C.c_void_p()
-        _lib.check(L.nvfi_comm_init(C.byref(self.handle), C.c_int(self.world), C.c_int(self.rank), ident))
+        _lib.check(L.nvfi_comm_init(C.byref(self.handle), self.world, self.rank, ident))
 
     def all_reduce_(self, flat, average=True):
         """in place, asynchronous on the current stream"""
         C = self._C
         assert flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous()
-        self._lib.check(self._lib.lib().nvfi_allreduce_grads(self.handle, self._lib.ptr(flat), C.c_int64(flat.numel()), C.c_int(1 if average else 0),
+        self._lib.check(self._lib.lib().nvfi_allreduce_grads(self.handle, self._lib.ptr(flat), flat.numel(), 1 if average else 0,
                                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return flat
 

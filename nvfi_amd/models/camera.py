@@ -129,16 +129,14 @@ class Camera(object):
         """Device-side variant of sample_rays (next-row f-2): pixel ids drawn on the GPU, rays generated by nvfi_gen_rays without
         materialising the H*W bundle.  n_rays DISTINCT pixels, like np.random.choice(replace=False) below (a device-side permutation;
         the fused driver's nvfi_draw_batch draws without replacement too, through a keyed bijection of the pixel range)."""
-        import ctypes as C
         from .. import _lib
         dev = self.pose.device
         ids = torch.randperm(self.height * self.width, device=dev, generator=generator)[:n_rays].contiguous()
         ro = torch.empty(n_rays, 3, device=dev)
         rd = torch.empty(n_rays, 3, device=dev)
         pose = self.pose[:3, :4].contiguous().float()
-        _lib.check(_lib.lib().nvfi_gen_rays(_lib.ptr(pose), C.c_int(self.height), C.c_int(self.width), C.c_float(float(self.focal)),
-                                            C.c_int64(n_rays), _lib.ptr(ids), _lib.ptr(ro), _lib.ptr(rd),
-                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.lib().nvfi_gen_rays(_lib.ptr(pose), self.height, self.width, float(self.focal), n_rays, _lib.ptr(ids),
+                                            _lib.ptr(ro), _lib.ptr(rd), _lib.stream_ptr()))
         return Ray(ro, rd, self.near, self.far), ids
 
     def sample_rays(self, n_rays):

@@ -23,9 +23,9 @@ class _RenderFn(torch.autograd.Function):
         t_dev = getattr(t, "dev", None)        # DeviceTime: the kernels read the time from device memory; float(t) is the launch plan
         t = float(t)
         desc, ws, (rgb, depth, acc, weights, counters) = field._ray_buffers(R, rays_o.device, t, flags)      # all 8 counters are written by the call
-        _lib.check(L.nvfi_render_fwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(jitter),
-                                       C.c_float(t), _lib.ptr(t_dev), C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc),
-                                       _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), _stream_ptr()))
+        _lib.check(L.nvfi_render_fwd_t(C.byref(desc), R, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(jitter),
+                                       t, _lib.ptr(t_dev), flags, _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc),
+                                       _lib.ptr(weights), _lib.ptr(ws), ws.numel(), _lib.ptr(counters), _stream_ptr()))
         field.last_counters = counters
         field._last_ws = ws if (flags & _lib.NVFI_WANT_MASK) else None
         field._last_call = (R, t, flags)
@@ -55,9 +55,9 @@ class _RenderFn(torch.autograd.Function):
         G = field._grads_struct(grads)
         gs = [None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_acc, g_weights)]
         R = rays_o.shape[0]
-        _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(rays_o), _lib.ptr(rays_d), C.c_float(ctx.t), C.c_int(int(ctx.t_on_device)),
-                                     C.c_int(ctx.flags), _lib.ptr(weights), _lib.ptr(gs[0]), _lib.ptr(gs[1]), _lib.ptr(gs[2]),
-                                     _lib.ptr(gs[3]), C.byref(G), _lib.ptr(ctx.ws), C.c_int64(ctx.ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_render_bwd_t(C.byref(desc), R, _lib.ptr(rays_o), _lib.ptr(rays_d), ctx.t, int(ctx.t_on_device),
+                                     ctx.flags, _lib.ptr(weights), _lib.ptr(gs[0]), _lib.ptr(gs[1]), _lib.ptr(gs[2]),
+                                     _lib.ptr(gs[3]), C.byref(G), _lib.ptr(ctx.ws), ctx.ws.numel(), _stream_ptr()))
         ctx.ws = None
         if inplace:
             return (None,) * (_RenderFn.N_ARGS + len(params))
@@ -74,7 +74,7 @@ class _PdeFn(torch.autograd.Function):
         dev = points.device
         P = points.shape[0]
         desc = field._desc()
-        nbytes = _lib.bytes_of(L.nvfi_pde_workspace_bytes, C.byref(desc), C.c_int64(P))
+        nbytes = _lib.bytes_of(L.nvfi_pde_workspace_bytes, C.byref(desc), P)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.zeros(4, device=dev)
         grads = _zero_grads(params)
@@ -87,9 +87,9 @@ class _PdeFn(torch.autograd.Function):
         # the weight gradients run on the field's PDE side stream - under the reference's loop, which waits for the value right after this call
         # (train_nvfi.py:233) and then differentiates the renders, the PDE adjoint overlaps with them; backward() waits for `ctx.done`
         side = field._side_stream("p") if field.pde_split else None
-        _lib.check(L.nvfi_pde_loss_split(C.byref(desc), C.c_int64(P), _lib.ptr(points), _lib.ptr(t), C.c_float(1.0), _lib.ptr(out),
-                                         C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters),
-                                         _lib.ptr(kept), _lib.ptr(jac), C.c_int64(int(field.pde_debug)), info, _stream_ptr(),
+        _lib.check(L.nvfi_pde_loss_split(C.byref(desc), P, _lib.ptr(points), _lib.ptr(t), 1.0, _lib.ptr(out),
+                                         C.byref(G), _lib.ptr(ws), ws.numel(), _lib.ptr(counters),
+                                         _lib.ptr(kept), _lib.ptr(jac), int(field.pde_debug), info, _stream_ptr(),
                                          C.c_void_p(side.cuda_stream) if side is not None else None))
         ctx.done = None
         if side is not None:
@@ -151,7 +151,7 @@ class _RegFn(torch.autograd.Function):
             rt["_reg_live"] = 0
             out = torch.empty(3, device=planes[0].device)
             desc = field._desc()
-            _lib.check(L.nvfi_plane_regs(C.byref(desc), C.c_float(0.0), C.c_float(0.0), C.c_float(0.0), _lib.ptr(out), None, _stream_ptr()))
+            _lib.check(L.nvfi_plane_regs(C.byref(desc), 0.0, 0.0, 0.0, _lib.ptr(out), None, _stream_ptr()))
             c = (key, out, torch.cuda.current_stream())
             rt["_reg_fwd"] = c
         elif c[2] != torch.cuda.current_stream():
@@ -310,10 +310,10 @@ class _AdvectFn(torch.autograd.Function):
         g = g.reshape(-1, 3).contiguous().float()
         N = x.shape[0]
         gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        t, t1 = C.c_float(ctx.t), C.c_float(ctx.t_target)
+        t, t1 = ctx.t, ctx.t_target
 
         def nbytes(n):
-            return _lib.bytes_of(L.nvfi_advect_grad_workspace_bytes, C.byref(desc), C.c_int64(n), t, t1)
+            return _lib.bytes_of(L.nvfi_advect_grad_workspace_bytes, C.byref(desc), n, t, t1)
 
         chunk, ws_bytes, chunks = _lib.plan_chunks(nbytes, N, ctx.max_ws, "advect", unit="point")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
@@ -321,8 +321,8 @@ class _AdvectFn(torch.autograd.Function):
         field.last_advect_workspace_bytes = ws.numel()
         for i in range(0, chunks * chunk, max(chunk, 1)):
             n = min(chunk, N - i)
-            _lib.check(L.nvfi_advect_grad(C.byref(desc), C.c_int64(n), _lib.ptr(x[i:i + n]), t, t1, _lib.ptr(g[i:i + n]),
-                                          None if gx is None else _lib.ptr(gx[i:i + n]), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+            _lib.check(L.nvfi_advect_grad(C.byref(desc), n, _lib.ptr(x[i:i + n]), t, t1, _lib.ptr(g[i:i + n]),
+                                          None if gx is None else _lib.ptr(gx[i:i + n]), C.byref(G), _lib.ptr(ws), ws.numel(), _stream_ptr()))
         return (None, gx, None, None, None) + tuple(grads)
 
 

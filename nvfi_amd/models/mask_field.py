@@ -34,12 +34,11 @@ class _MaskFn(torch.autograd.Function):
         pts = point.detach().contiguous().float()
         params_c = [p.detach().contiguous() for p in params]
         md = _mask_desc(mf, params_c)
-        nbytes = _lib.bytes_of(L.nvfi_maskfield_workspace_bytes, C.byref(md), C.c_int64(N), C.c_int(1 if train else 0))
+        nbytes = _lib.bytes_of(L.nvfi_maskfield_workspace_bytes, C.byref(md), N, 1 if train else 0)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
         out = torch.empty(N, mf.mask_dim, device=pts.device, dtype=torch.float32)
         mode = (1 if train else 0) | (2 if mf.mfma_fp16 else 0)
-        _lib.check(L.nvfi_maskfield_fwd(C.byref(md), C.c_int64(N), _lib.ptr(pts), _lib.ptr(out), C.c_int(mode),
-                                        _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_maskfield_fwd(C.byref(md), N, _lib.ptr(pts), _lib.ptr(out), mode, _lib.ptr(ws), ws.numel(), _stream_ptr()))
         ctx.mf, ctx.N, ctx.ws, ctx.params_c, ctx.train, ctx.mode = mf, N, ws, params_c, train, mode
         return out
 
@@ -55,8 +54,7 @@ class _MaskFn(torch.autograd.Function):
             mg.W[i] = _lib.ptr(grads[2 * i]); mg.b[i] = _lib.ptr(grads[2 * i + 1])
         g = g_out.contiguous().float()
         if ctx.N > 0:
-            _lib.check(L.nvfi_maskfield_bwd(C.byref(md), C.c_int64(ctx.N), _lib.ptr(g), C.byref(mg), C.c_int(ctx.mode), _lib.ptr(ctx.ws),
-                                            C.c_int64(ctx.ws.numel()), _stream_ptr()))
+            _lib.check(L.nvfi_maskfield_bwd(C.byref(md), ctx.N, _lib.ptr(g), C.byref(mg), ctx.mode, _lib.ptr(ctx.ws), ctx.ws.numel(), _stream_ptr()))
         ctx.ws = None
         return (None, None) + tuple(grads)
 

@@ -401,7 +401,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
                 nb = _lib.bytes_of(L.nvfi_frag_cache_bytes, C.byref(d))
                 buf = torch.empty(nb, dtype=torch.uint8, device=ps[0].device)
             d.frags = None
-            _lib.check(L.nvfi_pack_frags(C.byref(d), _lib.ptr(buf), C.c_int64(buf.numel()), C.c_void_p(cur.cuda_stream)))
+            _lib.check(L.nvfi_pack_frags(C.byref(d), _lib.ptr(buf), buf.numel(), C.c_void_p(cur.cuda_stream)))
             ev = torch.cuda.Event()
             ev.record(cur)
             fc = rt["_frag_cache"] = dict(key=key, buf=buf, event=ev, stream=cur, waited=set(), capture=cap)
@@ -418,7 +418,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         flags = (_lib.NVFI_TRAIN if train else 0) | (_lib.NVFI_TRANSFER if transfer else 0) | (_lib.NVFI_WANT_FLOW if flow else 0)
         if objects:
             flags |= _lib.NVFI_WANT_MASK | _lib.NVFI_WANT_SELECT
-        return _lib.bytes_of(_lib.lib().nvfi_render_workspace_bytes_t, C.byref(desc), C.c_int64(int(R)), C.c_int(flags), C.c_float(float(t)))
+        return _lib.bytes_of(_lib.lib().nvfi_render_workspace_bytes_t, C.byref(desc), int(R), flags, float(t))
 
     def invalidate_frags(self):
         """the weights were edited behind torch's version counters (p.data.copy_(), a raw kernel): the next call repacks"""
@@ -470,7 +470,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         """-> desc, workspace, (rgb, depth, acc, weights, counters) of a render of R rays at time t: the workspace as
         nvfi_render_workspace_bytes_t plans it, the outputs un-initialised (maps=False: no rgb / depth / acc - the caller has its own)"""
         desc = self._desc()
-        nbytes = _lib.bytes_of(_lib.lib().nvfi_render_workspace_bytes_t, C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(t))
+        nbytes = _lib.bytes_of(_lib.lib().nvfi_render_workspace_bytes_t, C.byref(desc), R, flags, t)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         rgb, depth, acc = (torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)) if maps else (None, None, None)
         weights = torch.empty(R, desc.n_samples, device=dev)
@@ -569,12 +569,11 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         vel_map, flow_map = torch.zeros(R, 3, device=dev), torch.zeros(R, 3, device=dev)
         flow2d = torch.zeros(R, 2, device=dev) if pose is not None else None
         if R > 0:
-            _lib.check(L.nvfi_render_fwd(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), None, C.c_float(t), C.c_int(flags),
-                                         _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
-                                         _lib.ptr(counters), _stream_ptr()))
-            _lib.check(L.nvfi_render_flow(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_float(dt), C.c_int(flags),
-                                          _lib.ptr(weights), _lib.ptr(pose), C.c_int(H), C.c_int(W), C.c_float(focal),
-                                          _lib.ptr(vel_map), _lib.ptr(flow_map), _lib.ptr(flow2d), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+            _lib.check(L.nvfi_render_fwd(C.byref(desc), R, _lib.ptr(ray_o), _lib.ptr(ray_d), None, t, flags, _lib.ptr(rgb), _lib.ptr(depth),
+                                         _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), ws.numel(), _lib.ptr(counters), _stream_ptr()))
+            _lib.check(L.nvfi_render_flow(C.byref(desc), R, _lib.ptr(ray_o), _lib.ptr(ray_d), t, dt, flags, _lib.ptr(weights), _lib.ptr(pose),
+                                          H, W, focal, _lib.ptr(vel_map), _lib.ptr(flow_map), _lib.ptr(flow2d), _lib.ptr(ws), ws.numel(),
+                                          _stream_ptr()))
             self.last_counters = counters
         return rgb, depth, acc, weights, vel_map, flow_map, flow2d
 
@@ -630,14 +629,13 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         mask_map, obj_rgb = torch.zeros(R, K, device=dev), torch.zeros(R, K, 3, device=dev)
         obj_acc, obj_depth = torch.zeros(R, K, device=dev), torch.zeros(R, K, device=dev)
         if R > 0:
-            _lib.check(L.nvfi_render_fwd_select(C.byref(desc), C.byref(md), _lib.ptr(sel), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), None,
-                                                C.c_float(t), C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights),
-                                                _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), _stream_ptr()))
-            _lib.check(L.nvfi_render_mask(C.byref(desc), C.byref(md), C.c_int64(R), C.c_float(t), C.c_int(flags), _lib.ptr(weights),
-                                          _lib.ptr(mask_map), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
-            _lib.check(L.nvfi_render_objects(C.byref(desc), C.byref(md), C.c_int64(R), C.c_float(t), C.c_int(flags), _lib.ptr(weights),
-                                             _lib.ptr(obj_rgb), _lib.ptr(obj_acc), _lib.ptr(obj_depth), _lib.ptr(ws), C.c_int64(ws.numel()),
-                                             _stream_ptr()))
+            _lib.check(L.nvfi_render_fwd_select(C.byref(desc), C.byref(md), _lib.ptr(sel), R, _lib.ptr(ray_o), _lib.ptr(ray_d), None, t, flags,
+                                                _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), ws.numel(),
+                                                _lib.ptr(counters), _stream_ptr()))
+            _lib.check(L.nvfi_render_mask(C.byref(desc), C.byref(md), R, t, flags, _lib.ptr(weights), _lib.ptr(mask_map), _lib.ptr(ws),
+                                          ws.numel(), _stream_ptr()))
+            _lib.check(L.nvfi_render_objects(C.byref(desc), C.byref(md), R, t, flags, _lib.ptr(weights), _lib.ptr(obj_rgb), _lib.ptr(obj_acc),
+                                             _lib.ptr(obj_depth), _lib.ptr(ws), ws.numel(), _stream_ptr()))
             self.last_counters = counters
         return rgb, depth, acc, weights, mask_map, obj_rgb, obj_acc, obj_depth
 
@@ -659,8 +657,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         xyz = torch.empty(M, 3, device=dev)
         idx = torch.empty(M, dtype=torch.int64, device=dev)
         ws = self._last_ws
-        _lib.check(L.nvfi_render_export_masked(C.byref(desc), C.c_int64(R), C.c_float(t), C.c_int(flags), _lib.ptr(ws), C.c_int64(ws.numel()),
-                                               C.c_int64(M), _lib.ptr(xyz), _lib.ptr(idx), _stream_ptr()))
+        _lib.check(L.nvfi_render_export_masked(C.byref(desc), R, t, flags, _lib.ptr(ws), ws.numel(), M, _lib.ptr(xyz), _lib.ptr(idx), _stream_ptr()))
         mask = self.mask_field(xyz)
         S = weights.shape[1]
         w = weights.reshape(-1)[idx]
@@ -675,8 +672,8 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         out = torch.empty(R, mf.mask_dim, device=weights.device)
         desc = self._desc()
         ws = self._last_ws
-        _lib.check(L.nvfi_render_mask(C.byref(desc), C.byref(md), C.c_int64(R), C.c_float(t), C.c_int(flags), _lib.ptr(weights.detach()),
-                                      _lib.ptr(out), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_render_mask(C.byref(desc), C.byref(md), R, t, flags, _lib.ptr(weights.detach()), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                      _stream_ptr()))
         return out
 
     # ------------------------------------------------------------------ building blocks (inference, no autograd)
@@ -696,11 +693,10 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         xt = xt.reshape(-1, 4).contiguous().float()
         N = xt.shape[0]
         desc = self._desc()
-        nb = _lib.bytes_of(L.nvfi_vel_workspace_bytes, C.byref(desc), C.c_int64(N))
+        nb = _lib.bytes_of(L.nvfi_vel_workspace_bytes, C.byref(desc), N)
         ws = torch.empty(nb, dtype=torch.uint8, device=xt.device)
         u = torch.zeros(N, 6, device=xt.device)
-        _lib.check(L.nvfi_vel_eval(C.byref(desc), C.c_int64(N), _lib.ptr(xt), _lib.ptr(u), C.c_int(int(gated)), _lib.ptr(ws),
-                                   C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_vel_eval(C.byref(desc), N, _lib.ptr(xt), _lib.ptr(u), int(gated), _lib.ptr(ws), ws.numel(), _stream_ptr()))
         return u[:, :3].contiguous() if gated else u
 
     @torch.no_grad()
@@ -715,11 +711,11 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         bb = base_times.reshape(-1).contiguous().float()
         N = x.shape[0]
         desc = self._desc()
-        nb = _lib.bytes_of(L.nvfi_vel_workspace_bytes, C.byref(desc), C.c_int64(N))
+        nb = _lib.bytes_of(L.nvfi_vel_workspace_bytes, C.byref(desc), N)
         ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
         out = torch.empty_like(x)
-        _lib.check(L.nvfi_integrate_pos(C.byref(desc), C.c_int64(N), _lib.ptr(x), _lib.ptr(tt), _lib.ptr(bb), _lib.ptr(out),
-                                        _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_integrate_pos(C.byref(desc), N, _lib.ptr(x), _lib.ptr(tt), _lib.ptr(bb), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                        _stream_ptr()))
         return out
 
     def advect(self, pos, t, t_target, max_workspace_bytes=1 << 30):
@@ -752,7 +748,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         if wants and (desc.vel_fp16 & 3) in (1, 2):
             raise NotImplementedError("advect: the fp16-input modes (vel_fp16 1 / 2) have no adjoint")
         if (desc.vel_fp16 & 3) not in (1, 2):      # the step limit, decided on the host before anything is launched
-            _lib.bytes_of(_lib.lib().nvfi_advect_grad_workspace_bytes, C.byref(desc), C.c_int64(0), C.c_float(ts), C.c_float(t1s))
+            _lib.bytes_of(_lib.lib().nvfi_advect_grad_workspace_bytes, C.byref(desc), 0, ts, t1s)
         x = pos.reshape(-1, 3).contiguous().float()
         if not wants:
             tt = torch.full((x.shape[0],), ts, dtype=torch.float32, device=x.device)
@@ -768,7 +764,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         feat = torch.empty(N, device=q.device)
         sigma = torch.empty(N, device=q.device)
         desc = self._desc()
-        _lib.check(L.nvfi_density_at(C.byref(desc), C.c_int64(N), _lib.ptr(q), _lib.ptr(feat), _lib.ptr(sigma), _stream_ptr()))
+        _lib.check(L.nvfi_density_at(C.byref(desc), N, _lib.ptr(q), _lib.ptr(feat), _lib.ptr(sigma), _stream_ptr()))
         return feat.unsqueeze(-1)
 
     def lookup_density(self, xyzt):
@@ -810,7 +806,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         v = viewdirs.reshape(-1, 3).contiguous().float()
         ft = features.reshape(-1, 27).contiguous().float()
         rgb = torch.empty(v.shape[0], 3, device=v.device)
-        _lib.check(L.nvfi_sh_render(C.c_int64(v.shape[0]), _lib.ptr(v), _lib.ptr(ft), _lib.ptr(rgb), _stream_ptr()))
+        _lib.check(L.nvfi_sh_render(v.shape[0], _lib.ptr(v), _lib.ptr(ft), _lib.ptr(rgb), _stream_ptr()))
         return rgb
 
     def feature2density(self, density_features, x=None):
@@ -825,10 +821,9 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         N = q.shape[0]
         rgb = torch.empty(N, 3, device=q.device)
         desc = self._desc()
-        nb = _lib.bytes_of(L.nvfi_app_workspace_bytes, C.byref(desc), C.c_int64(N))
+        nb = _lib.bytes_of(L.nvfi_app_workspace_bytes, C.byref(desc), N)
         ws = torch.empty(nb, dtype=torch.uint8, device=q.device)
-        _lib.check(L.nvfi_app_at(C.byref(desc), C.c_int64(N), _lib.ptr(q), _lib.ptr(v), _lib.ptr(rgb), _lib.ptr(ws),
-                                 C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_app_at(C.byref(desc), N, _lib.ptr(q), _lib.ptr(v), _lib.ptr(rgb), _lib.ptr(ws), ws.numel(), _stream_ptr()))
         return rgb
 
     def _render_module_call(self, pts, viewdirs, features):
@@ -841,10 +836,9 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         N = x.shape[0]
         rgb = torch.empty(N, 3, device=x.device)
         desc = self._desc()
-        nb = _lib.bytes_of(L.nvfi_app_workspace_bytes, C.byref(desc), C.c_int64(N))
+        nb = _lib.bytes_of(L.nvfi_app_workspace_bytes, C.byref(desc), N)
         ws = torch.empty(2 * nb, dtype=torch.uint8, device=x.device)
-        _lib.check(L.nvfi_render_mlp(C.byref(desc), C.c_int64(N), _lib.ptr(x), _lib.ptr(v), _lib.ptr(fe), _lib.ptr(rgb), _lib.ptr(ws),
-                                     C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_render_mlp(C.byref(desc), N, _lib.ptr(x), _lib.ptr(v), _lib.ptr(fe), _lib.ptr(rgb), _lib.ptr(ws), ws.numel(), _stream_ptr()))
         return rgb
 
     def shade(self, pts, viewdirs, features, max_workspace_bytes=1 << 30):
@@ -896,7 +890,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         t = t.reshape(-1).contiguous().float()
         P = points.shape[0]
         desc = self._desc()
-        nbytes = _lib.bytes_of(L.nvfi_pde_workspace_bytes, C.byref(desc), C.c_int64(P))
+        nbytes = _lib.bytes_of(L.nvfi_pde_workspace_bytes, C.byref(desc), P)
         ws = self._scratch("pde", nbytes, points.device)
         out = torch.empty(4, device=points.device)       # written by k_pde_finish
         if grad_targets is not None:
@@ -909,12 +903,11 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         if isinstance(weight, torch.Tensor):     # the weight lives in device memory (hipGraph replay: it decays every iteration)
             if not (weight.is_cuda and weight.dtype == torch.float32 and weight.numel() == 1):
                 raise _lib.NvfiError("a device-side PDE weight must be a 1-element fp32 CUDA tensor")
-            _lib.check(L.nvfi_pde_loss_dev(C.byref(desc), C.c_int64(P), _lib.ptr(points), _lib.ptr(t), _lib.ptr(weight), _lib.ptr(out),
-                                           C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), _stream_ptr()))
+            _lib.check(L.nvfi_pde_loss_dev(C.byref(desc), P, _lib.ptr(points), _lib.ptr(t), _lib.ptr(weight), _lib.ptr(out), C.byref(G), _lib.ptr(ws),
+                                           ws.numel(), _lib.ptr(counters), _stream_ptr()))
         else:
-            _lib.check(L.nvfi_pde_loss_ex(C.byref(desc), C.c_int64(P), _lib.ptr(points), _lib.ptr(t), C.c_float(float(weight)), _lib.ptr(out),
-                                          C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), None, None, C.c_int64(0), None,
-                                          _stream_ptr()))
+            _lib.check(L.nvfi_pde_loss_ex(C.byref(desc), P, _lib.ptr(points), _lib.ptr(t), float(weight), _lib.ptr(out), C.byref(G), _lib.ptr(ws),
+                                          ws.numel(), _lib.ptr(counters), None, None, 0, None, _stream_ptr()))
         self.last_pde_out, self.last_pde_counters = out, counters
         self.last_pde_n_kept = None
         return out
@@ -940,7 +933,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         pts = points.detach().reshape(-1, 3).contiguous().float()
         N = pts.shape[0]
         desc = self._desc() if params is None else self._desc(self._params_with(fs.PLANES, params))
-        nb = _lib.bytes_of(L.nvfi_char_workspace_bytes, C.byref(desc), C.c_int64(N))
+        nb = _lib.bytes_of(L.nvfi_char_workspace_bytes, C.byref(desc), N)
         ws = self._scratch("char", nb, pts.device)
         terms = torch.empty(2, device=pts.device)
         points0 = torch.empty_like(pts)
@@ -950,8 +943,8 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
                 if g is not None and g.stride() != p.stride():
                     raise _lib.NvfiError("a gradient target must share the memory layout of its parameter (channels_last planes)")
             G = C.byref(self._grads_struct(list(grads)))
-        _lib.check(L.nvfi_char_loss(C.byref(desc), C.c_int64(N), _lib.ptr(pts), C.c_float(float(t)), C.c_float(float(weight)), _lib.ptr(terms),
-                                    _lib.ptr(points0), G, _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_char_loss(C.byref(desc), N, _lib.ptr(pts), float(t), float(weight), _lib.ptr(terms), _lib.ptr(points0), G, _lib.ptr(ws),
+                                    ws.numel(), _stream_ptr()))
         return terms, points0
 
     def characteristic_loss_at(self, points, t, return_points0=False):
@@ -1102,24 +1095,23 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
                 raise ValueError(f"target_depth must hold one depth per ray ({R}) unless depth_index selects from an image")
             g_depth = out[o_gd:o_gd + R]
         st = _stream_ptr()
-        _lib.check(L.nvfi_render_fwd_mse(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(jitter), C.c_float(t), _lib.ptr(t_dev),
-                                         C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), C.c_int64(ws.numel()),
-                                         _lib.ptr(counters), _lib.ptr(target), C.c_float(float(loss_scale)), _lib.ptr(loss), _lib.ptr(g_rgb), st))
+        _lib.check(L.nvfi_render_fwd_mse(C.byref(desc), R, _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(jitter), t, _lib.ptr(t_dev), flags, _lib.ptr(rgb),
+                                         _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), ws.numel(), _lib.ptr(counters),
+                                         _lib.ptr(target), float(loss_scale), _lib.ptr(loss), _lib.ptr(g_rgb), st))
         self.last_counters = counters
         if g_depth is not None:       # the int64 count of the entries that took part sits behind the depth loss
-            _lib.check(L.nvfi_depth_loss(C.c_int64(R), _lib.ptr(depth), _lib.ptr(target_depth), _lib.ptr(depth_index),
-                                         C.c_int(_lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0), C.c_float(float(loss_scale) * float(depth_weight)),
+            _lib.check(L.nvfi_depth_loss(R, _lib.ptr(depth), _lib.ptr(target_depth), _lib.ptr(depth_index),
+                                         _lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0, float(loss_scale) * float(depth_weight),
                                          _lib.ptr(loss[_LOSS_DEPTH:]), _lib.ptr(g_depth), _lib.ptr(loss[_LOSS_DEPTH_COUNT:]), st))
         g_w = None
         if distortion_weight > 0.0:
-            dbytes = _lib.bytes_of(L.nvfi_ray_distortion_workspace_bytes, C.c_int64(R))
+            dbytes = _lib.bytes_of(L.nvfi_ray_distortion_workspace_bytes, R)
             dws = out[o_dw:]
             if dbytes > dws.numel() * 4:
                 raise _lib.NvfiError(f"nvfi_ray_distortion wants a workspace of {dbytes} bytes, {dws.numel() * 4} were set aside")
             g_w = torch.empty(R, S, device=dev)
-            _lib.check(L.nvfi_ray_distortion(C.c_int64(R), C.c_int(S), _lib.ptr(weights), C.c_float(self.distortion_delta()),
-                                             C.c_float(float(loss_scale) * distortion_weight), None, _lib.ptr(loss[_LOSS_DISTORTION:]), None, _lib.ptr(g_w),
-                                             _lib.ptr(dws), C.c_int64(dws.numel() * 4), st))
+            _lib.check(L.nvfi_ray_distortion(R, S, _lib.ptr(weights), self.distortion_delta(), float(loss_scale) * distortion_weight, None,
+                                             _lib.ptr(loss[_LOSS_DISTORTION:]), None, _lib.ptr(g_w), _lib.ptr(dws), dws.numel() * 4, st))
         flow_call = None
         if target_flow is not None:
             from ..utils import flow_loss as fl
@@ -1143,8 +1135,10 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         if wait_before_backward is not None:
             torch.cuda.current_stream().wait_stream(wait_before_backward)
         G = self._grads_struct_cached(ps)
-        _lib.check(L.nvfi_render_bwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), C.c_float(t), C.c_int(int(t_dev is not None)),
-                                       C.c_int(flags), _lib.ptr(weights), _lib.ptr(g_rgb), _lib.ptr(g_depth), None, _lib.ptr(g_w_mask if mask_call is not None else g_w if flow_call is None else g_w_flow), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), st))
+        _lib.check(L.nvfi_render_bwd_t(C.byref(desc), R, _lib.ptr(ray_o), _lib.ptr(ray_d), t, int(t_dev is not None), flags, _lib.ptr(weights),
+                                       _lib.ptr(g_rgb), _lib.ptr(g_depth), None,
+                                       _lib.ptr(g_w_mask if mask_call is not None else g_w if flow_call is None else g_w_flow), C.byref(G),
+                                       _lib.ptr(ws), ws.numel(), st))
         res = (loss[_LOSS_MSE], rgb) if g_depth is None else (loss[_LOSS_MSE], rgb, loss[_LOSS_DEPTH])
         if g_w is not None:
             res = res + (loss[_LOSS_DISTORTION],)
@@ -1222,9 +1216,8 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
             jitter = jitter.reshape(-1).float().contiguous()
         desc, ws, (rgb, depth, acc, weights, counters) = self._ray_buffers(R, ray_o.device, t, flags)
         st = _stream_ptr()
-        _lib.check(L.nvfi_render_fwd_t(C.byref(desc), C.c_int64(R), _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(jitter), C.c_float(t), None,
-                                       C.c_int(flags), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws),
-                                       C.c_int64(ws.numel()), _lib.ptr(counters), st))
+        _lib.check(L.nvfi_render_fwd_t(C.byref(desc), R, _lib.ptr(ray_o), _lib.ptr(ray_d), _lib.ptr(jitter), t, None, flags, _lib.ptr(rgb),
+                                       _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(weights), _lib.ptr(ws), ws.numel(), _lib.ptr(counters), st))
         self.last_counters = counters
         md = _mask_desc(mask_field, mparams)
         call = ml.mask_loss_raw(desc, md, ws, flags, weights, t, target_mask, kind=kind, eps=eps, grad_scale=float(loss_scale), g_weights=False,
@@ -1361,7 +1354,7 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
                 raise _lib.NvfiError("device-side regulariser weights must be a contiguous fp32[3] CUDA tensor")
             _lib.check(L.nvfi_plane_regs_dev(C.byref(desc), _lib.ptr(w_l1), _lib.ptr(out), C.byref(G), _stream_ptr()))
             return out
-        _lib.check(L.nvfi_plane_regs(C.byref(desc), C.c_float(w_l1), C.c_float(w_tv_density), C.c_float(w_tv_app), _lib.ptr(out),
+        _lib.check(L.nvfi_plane_regs(C.byref(desc), w_l1, w_tv_density, w_tv_app, _lib.ptr(out),
                                      C.byref(G), _stream_ptr()))
         return out
 
@@ -1416,11 +1409,11 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         N = flat.shape[0]
         alpha = torch.zeros(N, device=dev)
         desc = self._desc()
-        nb = _lib.bytes_of(L.nvfi_alpha_workspace_bytes, C.byref(desc), C.c_int64(N))
+        nb = _lib.bytes_of(L.nvfi_alpha_workspace_bytes, C.byref(desc), N)
         ws = self._scratch("alpha", nb, dev)
         for t in (np.linspace(0, 59, 60) / 60):
-            _lib.check(L.nvfi_compute_alpha(C.byref(desc), C.c_int64(N), _lib.ptr(flat), C.c_float(float(np.float32(t))), C.c_int(int(transfer)),
-                                            C.c_float(self._step_host), C.c_int(1), _lib.ptr(alpha), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+            _lib.check(L.nvfi_compute_alpha(C.byref(desc), N, _lib.ptr(flat), float(np.float32(t)), int(transfer), self._step_host, 1,
+                                            _lib.ptr(alpha), _lib.ptr(ws), ws.numel(), _stream_ptr()))
         return alpha.view(gridSize[0], gridSize[1], gridSize[2]), dense_xyz
 
     @torch.no_grad()

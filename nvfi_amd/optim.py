@@ -4,7 +4,6 @@ Drop-in for `torch.optim.Adam(groups, betas=(0.9, 0.99))` as train_nvfi.py:88-96
 learning rates that the training loop rescales every iteration): same update rule, same `state_dict()` layout (`step`, `exp_avg`,
 `exp_avg_sq` per parameter), so optimiser checkpoints interchange with the reference's.  `step(zero_grad=True)` also clears the gradients in
 the same pass (the reference's separate `optimizer.zero_grad()` becomes a no-op on already-zero buffers)."""
-import ctypes as C
 
 import torch
 
@@ -90,7 +89,7 @@ class Adam(torch.optim.Optimizer):
                     g = torch.empty_like(p, memory_format=torch.preserve_format).copy_(g)
                     p.grad = g
                 batches.setdefault((float(b1), float(b2), float(group["eps"]), st["step"]), []).append((p, g, st, lr))
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = _lib.stream_ptr()
         global GENERATION
         GENERATION += 1
         cache = self.__dict__.setdefault("_tables", {})
@@ -112,9 +111,7 @@ class Adam(torch.optim.Optimizer):
             if hyper_dev is not None:
                 if len(batches) != 1 or hyper_dev.numel() < 1 + len(items) or not hyper_dev.is_cuda or hyper_dev.dtype != torch.float32:
                     raise _lib.NvfiError("step(hyper_dev=...) needs one batch and an fp32 CUDA tensor of 1 + n_tensors values")
-                _lib.check(L.nvfi_adam_step_dev(arr, C.c_int(len(items)), C.c_float(b1), C.c_float(b2), C.c_float(eps), _lib.ptr(hyper_dev),
-                                                C.c_int(1 if zero_grad else 0), stream))
+                _lib.check(L.nvfi_adam_step_dev(arr, len(items), b1, b2, eps, _lib.ptr(hyper_dev), 1 if zero_grad else 0, stream))
                 continue
-            _lib.check(L.nvfi_adam_step(arr, C.c_int(len(items)), C.c_float(b1), C.c_float(b2), C.c_float(eps), C.c_int64(step),
-                                        C.c_int(1 if zero_grad else 0), stream))
+            _lib.check(L.nvfi_adam_step(arr, len(items), b1, b2, eps, step, 1 if zero_grad else 0, stream))
         return loss

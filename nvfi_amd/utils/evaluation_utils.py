@@ -52,7 +52,6 @@ def depth_loss_raw(pred, gt, gt_index=None, skip_holes=False, grad_scale=1.0, ou
     (check_index=True: one min / max over the indices and a wait for it; an index outside gt raises IndexError before anything is launched).
     check_index=False leaves that out - no torch launch, no wait - for indices that are known to be in range, and inside a hipGraph capture.
     out: the three tensors to write into."""
-    import ctypes as C
     from .. import _lib
     if not (pred.is_cuda and gt.is_cuda and (gt_index is None or gt_index.is_cuda)):
         raise _lib.NvfiError("NVFi HIP kernels need tensors on the GPU (no CPU fallback exists)")
@@ -71,9 +70,9 @@ def depth_loss_raw(pred, gt, gt_index=None, skip_holes=False, grad_scale=1.0, ou
     if out is None:
         out = (torch.empty((), device=pred.device), torch.empty(n, device=pred.device), torch.empty((), dtype=torch.int64, device=pred.device))
     loss, g_pred, n_counted = out
-    _lib.check(_lib.lib().nvfi_depth_loss(C.c_int64(n), _lib.ptr(pred), _lib.ptr(gt), _lib.ptr(gt_index),
-                                          C.c_int(_lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0), C.c_float(float(grad_scale)),
-                                          _lib.ptr(loss), _lib.ptr(g_pred), _lib.ptr(n_counted), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    _lib.check(_lib.lib().nvfi_depth_loss(n, _lib.ptr(pred), _lib.ptr(gt), _lib.ptr(gt_index),
+                                          _lib.NVFI_DEPTH_SKIP_HOLES if skip_holes else 0, float(grad_scale),
+                                          _lib.ptr(loss), _lib.ptr(g_pred), _lib.ptr(n_counted), _lib.stream_ptr()))
     return loss, g_pred, n_counted
 
 

@@ -44,7 +44,7 @@ def density_grad_raw(desc, xyzt, g_feat, g_xyzt=True, grads=None):
     q = _points(xyzt)
     g = _upstream(g_feat, (q.shape[0],))
     out = _coord_out(g_xyzt, q)
-    _lib.check(_lib.lib().nvfi_density_grad(C.byref(desc), C.c_int64(q.shape[0]), _lib.ptr(q), _lib.ptr(g), _lib.ptr(out),
+    _lib.check(_lib.lib().nvfi_density_grad(C.byref(desc), q.shape[0], _lib.ptr(q), _lib.ptr(g), _lib.ptr(out),
                                             None if grads is None else C.byref(grads), _stream_ptr()))
     return out
 
@@ -57,7 +57,7 @@ def appfeat_raw(desc, xyzt, out=None):
         out = torch.empty(shape, device=q.device)
     elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != shape:
         raise ValueError(f"out: a contiguous float32 device tensor of shape {shape} expected")
-    _lib.check(_lib.lib().nvfi_appfeat_at(C.byref(desc), C.c_int64(q.shape[0]), _lib.ptr(q), _lib.ptr(out), _stream_ptr()))
+    _lib.check(_lib.lib().nvfi_appfeat_at(C.byref(desc), q.shape[0], _lib.ptr(q), _lib.ptr(out), _stream_ptr()))
     return out
 
 
@@ -67,7 +67,7 @@ def appfeat_grad_raw(desc, xyzt, g_feat, g_xyzt=True, grads=None):
     q = _points(xyzt)
     g = _upstream(g_feat, (q.shape[0], int(desc.app_dim)))
     out = _coord_out(g_xyzt, q)
-    _lib.check(_lib.lib().nvfi_appfeat_grad(C.byref(desc), C.c_int64(q.shape[0]), _lib.ptr(q), _lib.ptr(g), _lib.ptr(out),
+    _lib.check(_lib.lib().nvfi_appfeat_grad(C.byref(desc), q.shape[0], _lib.ptr(q), _lib.ptr(g), _lib.ptr(out),
                                             None if grads is None else C.byref(grads), _stream_ptr()))
     return out
 
@@ -84,7 +84,7 @@ def _out(want, shape, like, name):
 
 
 def render_mlp_grad_workspace_bytes(desc, n):
-    return _lib.bytes_of(_lib.lib().nvfi_render_mlp_grad_workspace_bytes, C.byref(desc), C.c_int64(n))
+    return _lib.bytes_of(_lib.lib().nvfi_render_mlp_grad_workspace_bytes, C.byref(desc), n)
 
 
 def render_mlp_grad_raw(desc, xyz, view, features, g_rgb, g_features=True, g_xyz=True, g_view=None, grads=None, workspace=None):
@@ -104,7 +104,7 @@ def render_mlp_grad_raw(desc, xyz, view, features, g_rgb, g_features=True, g_xyz
     gf, gx, gv = _out(g_features, (n, d), x, "g_features"), _out(g_xyz, (n, 3), x, "g_xyz"), _out(g_view, (n, 3), x, "g_view")
     if workspace is None:
         workspace = torch.empty(render_mlp_grad_workspace_bytes(desc, n), dtype=torch.uint8, device=x.device)
-    _lib.check(_lib.lib().nvfi_render_mlp_grad(C.byref(desc), C.c_int64(n), _lib.ptr(x), _lib.ptr(v), _lib.ptr(fe), _lib.ptr(g), _lib.ptr(gf),
+    _lib.check(_lib.lib().nvfi_render_mlp_grad(C.byref(desc), n, _lib.ptr(x), _lib.ptr(v), _lib.ptr(fe), _lib.ptr(g), _lib.ptr(gf),
                                                _lib.ptr(gx), _lib.ptr(gv), None if grads is None else C.byref(grads), _lib.ptr(workspace),
-                                               C.c_int64(workspace.numel()), _stream_ptr()))
+                                               workspace.numel(), _stream_ptr()))
     return gf, gx, gv

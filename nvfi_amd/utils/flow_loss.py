@@ -38,7 +38,7 @@ def flow_loss_plan(desc, R, t, dt, max_workspace_bytes=1 << 30):
     cap = int(R) * int(desc.n_samples)
 
     def nbytes(n):
-        return _lib.bytes_of(L.nvfi_flow_loss_workspace_bytes, C.byref(desc), C.c_int64(R), C.c_float(t), C.c_float(dt), C.c_int64(n))
+        return _lib.bytes_of(L.nvfi_flow_loss_workspace_bytes, C.byref(desc), R, t, dt, n)
 
     return _lib.plan_chunks(nbytes, cap, max_workspace_bytes, "flow loss")
 
@@ -82,11 +82,11 @@ def flow_loss_raw(desc, render_ws, flags, rays_o, rays_d, weights, t, dt, camera
     if add_gw and g_weights is None:
         raise ValueError("add_gw=True needs the g_weights tensor to add to")
     _lib.check(_lib.lib().nvfi_flow_loss_fwd(
-        C.byref(desc), C.c_int64(R), _lib.ptr(rays_o), _lib.ptr(rays_d), C.c_float(t), C.c_float(dt), C.c_int(int(flags)), _lib.ptr(weights),
-        _lib.ptr(pose), C.c_int(H), C.c_int(W), C.c_float(focal), _lib.ptr(target), _lib.ptr(valid), C.c_int(KINDS[kind]), C.c_float(float(huber_delta)),
-        C.c_float(float(grad_scale)), _lib.ptr(grad_scale_dev), C.c_int(_lib.NVFI_FLOWLOSS_ADD_GW if add_gw else 0),
-        _lib.ptr(loss), _lib.ptr(flow2d), _lib.ptr(g_weights), _lib.ptr(render_ws), C.c_int64(render_ws.numel()), C.c_int64(chunk),
-        _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        C.byref(desc), R, _lib.ptr(rays_o), _lib.ptr(rays_d), t, dt, int(flags), _lib.ptr(weights),
+        _lib.ptr(pose), H, W, focal, _lib.ptr(target), _lib.ptr(valid), KINDS[kind], float(huber_delta),
+        float(grad_scale), _lib.ptr(grad_scale_dev), _lib.NVFI_FLOWLOSS_ADD_GW if add_gw else 0,
+        _lib.ptr(loss), _lib.ptr(flow2d), _lib.ptr(g_weights), _lib.ptr(render_ws), render_ws.numel(), chunk,
+        _lib.ptr(ws), ws.numel(), _stream_ptr()))
     return dict(loss=loss, flow2d=flow2d, g_weights=g_weights, workspace=ws, chunk_cap=chunk, chunks=chunks, R=R, t=t, dt=dt)
 
 
@@ -96,5 +96,5 @@ def flow_loss_backward_raw(desc, call, G):
     L = _lib.lib()
     ws, chunk = call["workspace"], call["chunk_cap"]
     for k in range(call["chunks"]):
-        _lib.check(L.nvfi_flow_loss_bwd(C.byref(desc), C.c_int64(call["R"]), C.c_float(call["t"]), C.c_float(call["dt"]), C.c_int64(k * chunk),
-                                        C.c_int64(chunk), C.byref(G), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_flow_loss_bwd(C.byref(desc), call["R"], call["t"], call["dt"], k * chunk,
+                                        chunk, C.byref(G), _lib.ptr(ws), ws.numel(), _stream_ptr()))

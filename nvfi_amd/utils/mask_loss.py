@@ -30,7 +30,7 @@ def mask_loss_plan(desc, mdesc, R, max_workspace_bytes=1 << 30):
     cap = -(-int(R) * int(desc.n_samples) // 128) * 128           # whole 128-entry workgroups
 
     def nbytes(n):
-        return _lib.bytes_of(L.nvfi_mask_loss_workspace_bytes, C.byref(desc), C.byref(mdesc), C.c_int64(R), C.c_int64(n))
+        return _lib.bytes_of(L.nvfi_mask_loss_workspace_bytes, C.byref(desc), C.byref(mdesc), R, n)
 
     return _lib.plan_chunks(nbytes, cap, max_workspace_bytes, "mask loss")
 
@@ -81,10 +81,10 @@ def mask_loss_raw(desc, mdesc, render_ws, flags, weights, t, target, kind="ce", 
     if add_gw and g_weights is None:
         raise ValueError("add_gw=True needs the g_weights tensor to add to")
     _lib.check(_lib.lib().nvfi_mask_loss_fwd(
-        C.byref(desc), C.byref(mdesc), C.c_int64(R), C.c_float(t), C.c_int(int(flags)), _lib.ptr(weights), _lib.ptr(labels), _lib.ptr(soft),
-        C.c_int(KINDS[kind]), C.c_float(float(eps)), C.c_float(float(grad_scale)), _lib.ptr(grad_scale_dev),
-        C.c_int(_lib.NVFI_MASKLOSS_ADD_GW if add_gw else 0), _lib.ptr(loss), _lib.ptr(mask_map), _lib.ptr(g_weights),
-        _lib.ptr(render_ws), C.c_int64(render_ws.numel()), C.c_int64(chunk), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        C.byref(desc), C.byref(mdesc), R, t, int(flags), _lib.ptr(weights), _lib.ptr(labels), _lib.ptr(soft),
+        KINDS[kind], float(eps), float(grad_scale), _lib.ptr(grad_scale_dev),
+        _lib.NVFI_MASKLOSS_ADD_GW if add_gw else 0, _lib.ptr(loss), _lib.ptr(mask_map), _lib.ptr(g_weights),
+        _lib.ptr(render_ws), render_ws.numel(), chunk, _lib.ptr(ws), ws.numel(), _stream_ptr()))
     return dict(loss=loss, mask_map=mask_map, g_weights=g_weights, workspace=ws, chunk_cap=chunk, chunks=chunks, R=R, S=S, target=(labels, soft))
 
 
@@ -102,5 +102,5 @@ def mask_loss_backward_raw(mdesc, call, MG):
     L = _lib.lib()
     ws, chunk = call["workspace"], call["chunk_cap"]
     for k in range(call["chunks"]):
-        _lib.check(L.nvfi_mask_loss_bwd(C.byref(mdesc), C.c_int64(call["R"]), C.c_int(call["S"]), C.c_int64(k * chunk), C.c_int64(chunk),
-                                        C.byref(MG), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(L.nvfi_mask_loss_bwd(C.byref(mdesc), call["R"], call["S"], k * chunk, chunk,
+                                        C.byref(MG), _lib.ptr(ws), ws.numel(), _stream_ptr()))

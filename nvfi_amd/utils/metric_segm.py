@@ -16,7 +16,6 @@ N^2 - sum a_i^2 - sum b_j^2 + 2 sum n_ij^2, exact in integers - the reference's 
 Differences: labels must lie in [0, 32) (G <= 32; K <= 32) - a label outside is reported (NvfiError) when the results are read, a deferred
 check; `calculate_AP(plot=True)` raises; with ignore_npoint_thresh > 0 the confidence of a kept prediction is that prediction's own mean (the
 reference indexes the pixels of the j-th prediction BEFORE dropping the invalid ones, which mixes two predictions whenever one was dropped)."""
-import ctypes as C
 
 import numpy as np
 import torch
@@ -51,9 +50,8 @@ def segm_confusion(mask, segm, n_gt=None, want_pred=False):
     bad = torch.empty(B, dtype=torch.int32, device=dev)
     pred = torch.empty(B, N, dtype=torch.int32, device=dev) if want_pred else None
     lib = _lib.lib()
-    nbytes = C.c_int64(0)
-    _lib.check(lib.nvfi_metrics_workspace_bytes(1, B, K, 0, 0, C.byref(nbytes)))
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    nbytes = _lib.bytes_of(lib.nvfi_metrics_workspace_bytes, 1, B, K, 0, 0)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.nvfi_segm_confusion(B, N, K, G, _lib.ptr(mask), _lib.ptr(segm), _lib.ptr(counts), _lib.ptr(conf), _lib.ptr(pred),
                                            _lib.ptr(bad), _lib.ptr(ws), ws.numel(), _stream_ptr()))

@@ -64,9 +64,8 @@ def ssim_stats(pred, gt, layout="BCHW", L=None, per_image_range=False):
     win = (C.c_float * 11)(*SSIM().gaussian(11, 1.5).tolist())
     out = torch.empty(B, 2, dtype=torch.float64, device=pred.device)
     lib = _lib.lib()
-    nbytes = C.c_int64(0)
-    _lib.check(lib.nvfi_metrics_workspace_bytes(0, B, Cc, H, W, C.byref(nbytes)))
-    ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=pred.device)
+    nbytes = _lib.bytes_of(lib.nvfi_metrics_workspace_bytes, 0, B, Cc, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     mode = 0 if L is not None else (2 if per_image_range else 1)
     with torch.cuda.device(pred.device):
         _lib.check(lib.nvfi_ssim(B, Cc, H, W, _lib.ptr(pred), ps, _lib.ptr(gt), gs, win, float(L or 0.0), mode, _lib.ptr(out),

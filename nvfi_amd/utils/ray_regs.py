@@ -9,7 +9,6 @@ in normalised distance s = (z - near) / (far - near) every interval has the widt
     D_r = delta [ sum_i sum_j w_i w_j |i - j| + (1/3) sum_i w_i^2 ],     loss = (1/R) sum_r D_r
 
 csrc/raydist.hip forms the value and d loss / d weights in one kernel launch (+ one single-workgroup launch for the mean over rays)."""
-import ctypes as C
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -20,9 +19,8 @@ from .._lib import stream_ptr as _stream_ptr
 
 def distortion_workspace(R, device):
     """the workspace of one nvfi_ray_distortion call on R rays (uint8 device tensor)"""
-    nbytes = C.c_int64(0)
-    _lib.check(_lib.lib().nvfi_ray_distortion_workspace_bytes(C.c_int64(R), C.byref(nbytes)))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    nbytes = _lib.bytes_of(_lib.lib().nvfi_ray_distortion_workspace_bytes, R)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 def distortion_loss_raw(weights, delta, grad_scale=1.0, grad_scale_dev=None, out=None, want_per_ray=False, workspace=None):
@@ -50,9 +48,9 @@ def distortion_loss_raw(weights, delta, grad_scale=1.0, grad_scale_dev=None, out
             raise ValueError(f"out: a contiguous float32 device tensor of shape {shape} expected, got {tuple(o.shape)} {o.dtype}")
     if workspace is None and loss is not None:       # only the mean over rays uses it: a call without `loss` (the autograd backward) needs none
         workspace = distortion_workspace(R, dev)
-    _lib.check(_lib.lib().nvfi_ray_distortion(C.c_int64(R), C.c_int(S), _lib.ptr(weights), C.c_float(float(delta)), C.c_float(float(grad_scale)),
+    _lib.check(_lib.lib().nvfi_ray_distortion(R, S, _lib.ptr(weights), float(delta), float(grad_scale),
                                               _lib.ptr(grad_scale_dev), _lib.ptr(loss), _lib.ptr(per_ray), _lib.ptr(g_w),
-                                              _lib.ptr(workspace), C.c_int64(0 if workspace is None else workspace.numel()), _stream_ptr()))
+                                              _lib.ptr(workspace), 0 if workspace is None else workspace.numel(), _stream_ptr()))
     return (loss, g_w, per_ray) if (want_per_ray or len(out) > 2) else (loss, g_w)
 
 

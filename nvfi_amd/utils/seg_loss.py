@@ -16,7 +16,6 @@ Behaviour kept from the reference, on purpose:
   * an object whose weighted moments contain a NaN (an all-zero mask column: 0 / 0) gets R = I, t = 0.
 Differences: neighbours are ordered by (squared distance, index), a total order (pytorch3d leaves ties open); `pc_transformed` is returned
 detached; rank_loss (unused by train_segm.py) is not provided; fit_motion_svd_batch forms pc2 as pc1 + (pc2 - pc1) in fp32."""
-import ctypes as C
 
 import torch
 
@@ -41,9 +40,8 @@ def _f32(t):
 
 
 def _workspace(N, K, k, device):
-    nbytes = C.c_int64(0)
-    _lib.check(_lib.lib().nvfi_segloss_workspace_bytes(C.c_int64(N), C.c_int(K), C.c_int(k), C.byref(nbytes)))
-    return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
+    nbytes = _lib.bytes_of(_lib.lib().nvfi_segloss_workspace_bytes, N, K, k)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 def knn_self(pc, k, radius, reverse=True, return_dist=False):
@@ -60,8 +58,8 @@ def knn_self(pc, k, radius, reverse=True, return_dist=False):
     re = torch.empty(N * k, dtype=torch.int32, device=pc.device) if reverse else None
     ws = _workspace(N, 0, k, pc.device)
     with torch.cuda.device(pc.device):
-        _lib.check(_lib.lib().nvfi_knn_self(C.c_int64(N), _lib.ptr(pc), C.c_int(k), C.c_float(radius), _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(rs),
-                                            _lib.ptr(re), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+        _lib.check(_lib.lib().nvfi_knn_self(N, _lib.ptr(pc), k, radius, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(rs),
+                                            _lib.ptr(re), _lib.ptr(ws), ws.numel(), _stream_ptr()))
     return idx, d2, rs, re
 
 
@@ -85,9 +83,9 @@ class _SegLossFn(torch.autograd.Function):
         ws = _workspace(N, K, k if nn is not None else 0, dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().nvfi_segloss(
-                C.c_int64(N), C.c_int(K), _lib.ptr(pc), _lib.ptr(flow), _lib.ptr(m), C.c_int(k), _lib.ptr(idx), _lib.ptr(rs), _lib.ptr(re),
-                C.c_int(loss_norm), C.c_float(eps), C.c_float(wd), C.c_float(ws_), C.c_float(we), C.c_float(1.0), C.c_int(0),
-                _lib.ptr(g), _lib.ptr(losses), _lib.ptr(R), _lib.ptr(t), _lib.ptr(pct), _lib.ptr(ws), C.c_int64(ws.numel()), _stream_ptr()))
+                N, K, _lib.ptr(pc), _lib.ptr(flow), _lib.ptr(m), k, _lib.ptr(idx), _lib.ptr(rs), _lib.ptr(re),
+                loss_norm, eps, wd, ws_, we, 1.0, 0,
+                _lib.ptr(g), _lib.ptr(losses), _lib.ptr(R), _lib.ptr(t), _lib.ptr(pct), _lib.ptr(ws), ws.numel(), _stream_ptr()))
         ctx.g = g
         ctx.mask_dtype = mask.dtype
         outs = (losses[3], losses, R, t, pct)

@@ -64,14 +64,12 @@ class _MseFn(__import__("torch").autograd.Function):
 
     @staticmethod
     def forward(ctx, x, target):
-        import ctypes as C
         import torch
         from .. import _lib
         xc, tc = x.contiguous(), target.contiguous()
         loss = torch.empty((), device=x.device)
         grad = torch.empty_like(xc)
-        _lib.check(_lib.lib().nvfi_mse(_lib.ptr(xc), _lib.ptr(tc), C.c_int64(xc.numel()), _lib.ptr(loss), _lib.ptr(grad),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _lib.check(_lib.lib().nvfi_mse(_lib.ptr(xc), _lib.ptr(tc), xc.numel(), _lib.ptr(loss), _lib.ptr(grad), _lib.stream_ptr()))
         ctx.save_for_backward(grad)
         return loss
 

@@ -11,10 +11,20 @@ from conftest import ROOT
 from helpers import make_model, load_meta
 
 
-def _header_functions():
+def _header_prototypes():
+    """[(name, return type, kinds)] of every prototype of include/nvfi_hip.h in the header's order: comments and preprocessor lines stripped,
+    then `ret name(params);`.  kinds: one letter per parameter - p for anything with a `*`, l int64_t, i int, f float (a scalar of another
+    type is a KeyError: the binding's table has no letter for it); `(void)` gives the empty string."""
     txt = open(os.path.join(ROOT, "include", "nvfi_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(nvfi_[a-z0-9_]+)\s*\(", txt)))
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = "\n".join(line for line in txt.split("\n") if not line.lstrip().startswith("#"))
+    out = []
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(nvfi_\w+)\s*\(([^()]*)\)\s*;", txt):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        kinds = "" if params == ["void"] else "".join(
+            "p" if "*" in p else {"int64_t": "l", "int": "i", "float": "f"}[p.rsplit(" ", 1)[0]] for p in params)
+        out.append((name, " ".join(ret.split()), kinds))
+    return out
 
 
 def test_library_exports_every_declared_symbol():
@@ -23,26 +33,90 @@ def test_library_exports_every_declared_symbol():
     from nvfi_amd.build import build
     build()
     L = C.CDLL(_lib.SO)
-    names = _header_functions()
-    assert len(names) >= 15
+    names = [n for n, _, _ in _header_prototypes()]
+    assert len(names) == len(set(names)) == 75
     for n in names:
         assert hasattr(L, n), f"{n} declared in include/nvfi_hip.h but not exported"
-    assert set(_lib.EXPORTS) <= set(names)
-    assert _lib.lib().nvfi_abi_version() == 5
+    assert set(_lib.EXPORTS) == set(names) and len(_lib.EXPORTS) == 75
+    assert _lib.lib().nvfi_abi_version() == 5 == _lib.ABI_VERSION
+
+
+def test_signature_table_matches_header():
+    """_lib.SIGNATURES is the header: the same 75 names in the same order, every row the header's parameter kinds position by position; and
+    lib() has turned every row into argtypes (restype stays ctypes' int except where the header returns something else)."""
+    import ctypes as C
+    from nvfi_amd import _lib
+    protos = _header_prototypes()
+    assert list(_lib.SIGNATURES) == [n for n, _, _ in protos] and _lib.EXPORTS == list(_lib.SIGNATURES)
+    kind_of = {"p": C.c_void_p, "l": C.c_int64, "i": C.c_int, "f": C.c_float}
+    L = _lib.lib()
+    for name, ret, kinds in protos:
+        assert _lib.SIGNATURES[name] == kinds, (name, _lib.SIGNATURES[name], kinds)
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(kinds), name
+        assert list(fn.argtypes) == [kind_of[k] for k in kinds], name
+        if name == "nvfi_last_error":
+            assert ret == "const char*" and fn.restype is C.c_char_p
+        else:
+            assert ret == "int" and fn.restype is C.c_int, (name, ret)
+    assert isinstance(L.nvfi_last_error(), bytes)
+
+
+def test_wrong_scalar_kind_is_refused_before_the_call():
+    """With argtypes set a wrapper of the wrong kind does not reach the library: ctypes raises while it converts the arguments, so nothing is
+    launched (no GPU needed).  One size query of each former group: nvfi_ray_distortion_workspace_bytes had a hand-written argtypes row,
+    nvfi_segloss_workspace_bytes had none."""
+    import ctypes as C
+    from nvfi_amd import _lib
+    L = _lib.lib()
+    nb = C.c_int64(-1)
+    for call in (
+        lambda: L.nvfi_ray_distortion_workspace_bytes(C.c_int(2048), C.byref(nb)),          # c_int for an int64_t
+        lambda: L.nvfi_segloss_workspace_bytes(C.c_int(2048), 4, 8, C.byref(nb)),
+        lambda: L.nvfi_segloss_workspace_bytes(2048, 4.0, 8, C.byref(nb)),                  # a Python float for an int
+        lambda: L.nvfi_ray_distortion_workspace_bytes(2048.0, C.byref(nb)),                 # ... and for an int64_t
+        lambda: L.nvfi_ray_distortion(8, 4, None, C.c_double(0.1), 1.0, None, None, None, None, None, 0, None),     # c_double for a float
+        lambda: L.nvfi_knn_self(8, None, 4, C.c_double(0.1), None, None, None, None, None, 0, None),
+    ):
+        with pytest.raises(C.ArgumentError):
+            call()
+        assert nb.value == -1
+    # plain numbers and correct wrappers both pass
+    assert L.nvfi_ray_distortion_workspace_bytes(2048, C.byref(nb)) == 0 and nb.value >= 2048 * 8
+    assert L.nvfi_ray_distortion_workspace_bytes(C.c_int64(2048), C.byref(nb)) == 0
+    assert L.nvfi_segloss_workspace_bytes(2048, 4, 8, C.byref(nb)) == 0 and nb.value > 0
+    assert _lib.bytes_of(L.nvfi_segloss_workspace_bytes, 2048, 4, 8) == nb.value
+
+
+def test_abi_version_is_checked_at_load(monkeypatch):
+    """lib() refuses a library whose nvfi_abi_version() is not the binding's ABI_VERSION, naming both numbers and the file"""
+    from nvfi_amd import _lib
+    _lib.lib()
+    monkeypatch.setattr(_lib, "ABI_VERSION", 6)
+    monkeypatch.setattr(_lib, "_LIB", None)
+    with pytest.raises(_lib.NvfiError) as e:
+        _lib.lib()
+    assert "5" in str(e.value) and "6" in str(e.value) and _lib.SO in str(e.value)
+    assert _lib._LIB is None
+    monkeypatch.undo()
+    assert _lib.ABI_VERSION == 5 and _lib.lib().nvfi_abi_version() == 5
 
 
 def test_struct_layout_matches_header():
-    """ctypes mirror of nvfi_field_desc / nvfi_grads has the size the C compiler gives the header's structs."""
+    """every ctypes mirror of a struct of the header has the size the C compiler gives it"""
     import subprocess, tempfile, ctypes as C
     from nvfi_amd import _lib
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nvfi_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu\\n", sizeof(nvfi_field_desc), sizeof(nvfi_grads), '
-           'sizeof(nvfi_draw_desc), offsetof(nvfi_field_desc, frags), offsetof(nvfi_draw_desc, points));return 0;}\n')
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "nvfi_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(nvfi_field_desc), '
+           'sizeof(nvfi_grads), sizeof(nvfi_draw_desc), offsetof(nvfi_field_desc, frags), offsetof(nvfi_draw_desc, points), '
+           'sizeof(nvfi_mask_desc), sizeof(nvfi_mask_grads), sizeof(nvfi_adam_tensor));return 0;}\n')
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
-        a, b, c, o1, o2 = map(int, subprocess.check_output([os.path.join(d, "s")]).split())
+        a, b, c, o1, o2, md, mg, at = map(int, subprocess.check_output([os.path.join(d, "s")]).split())
+    print("sizeof: mask_desc", md, C.sizeof(_lib.MaskDesc), "mask_grads", mg, C.sizeof(_lib.MaskGrads), "adam_tensor", at, C.sizeof(_lib.AdamTensor))
     assert C.sizeof(_lib.FieldDesc) == a and C.sizeof(_lib.Grads) == b and C.sizeof(_lib.DrawDesc) == c
     assert _lib.FieldDesc.frags.offset == o1 and _lib.DrawDesc.points.offset == o2      # ABI v5 additions
+    assert C.sizeof(_lib.MaskDesc) == md and C.sizeof(_lib.MaskGrads) == mg and C.sizeof(_lib.AdamTensor) == at
 
 
 @pytest.mark.parametrize("kind", ["A", "B"])

@@ -29,13 +29,12 @@ def test_exports_and_header():
     assert "raydist.hip" in SOURCES
     assert "nvfi_ray_distortion" in _lib.EXPORTS and "nvfi_ray_distortion_workspace_bytes" in _lib.EXPORTS
     assert os.path.exists(_lib.SO), "libnvfi_hip.so has not been built"
-    L = ctypes.CDLL(_lib.SO)
+    L = _lib.lib()      # the binding's table gives both functions their argtypes: plain numbers below
     assert hasattr(L, "nvfi_ray_distortion") and hasattr(L, "nvfi_ray_distortion_workspace_bytes") and L.nvfi_abi_version() == 5
     header = open(os.path.join(ROOT, "include", "nvfi_hip.h")).read()
     assert "int nvfi_ray_distortion(" in header and "int nvfi_ray_distortion_workspace_bytes(" in header
     # the workspace query is host code: it answers without a GPU, and refuses what it cannot size
     n = ctypes.c_int64(-1)
-    L.nvfi_ray_distortion_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     assert L.nvfi_ray_distortion_workspace_bytes(2048, ctypes.byref(n)) == 0 and n.value >= 2048 * 8
     assert L.nvfi_ray_distortion_workspace_bytes(-1, ctypes.byref(n)) == 2
 

@@ -53,20 +53,18 @@ def public_maps(f, cam, rays, chunk=32768):
     for c in range(0, o_all.shape[0], chunk):
         o, d = o_all[c:c + chunk].contiguous(), d_all[c:c + chunk].contiguous()
         R = o.shape[0]
-        nb = C.c_int64(0)
-        _lib.check(L.nvfi_render_workspace_bytes_t(C.byref(desc), C.c_int64(R), C.c_int(flags), C.c_float(T), C.byref(nb)))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        ws = torch.empty(_lib.bytes_of(L.nvfi_render_workspace_bytes_t, C.byref(desc), R, flags, T), dtype=torch.uint8, device=dev)
         rgb, depth, acc = torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev)
         w = torch.empty(R, S, device=dev)
         counters = torch.empty(_lib.NCOUNTERS, dtype=torch.int64, device=dev)
-        _lib.check(L.nvfi_render_fwd(C.byref(desc), C.c_int64(R), _lib.ptr(o), _lib.ptr(d), None, C.c_float(T), C.c_int(flags), _lib.ptr(rgb),
-                                     _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(w), _lib.ptr(ws), C.c_int64(ws.numel()), _lib.ptr(counters), _stream_ptr()))
+        _lib.check(L.nvfi_render_fwd(C.byref(desc), R, _lib.ptr(o), _lib.ptr(d), None, T, flags, _lib.ptr(rgb),
+                                     _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(w), _lib.ptr(ws), ws.numel(), _lib.ptr(counters), _stream_ptr()))
         M = int(counters[2])                             # waits for the device: the masked count sizes everything below
         xw = torch.empty(M, 3, device=dev)               # (the warped keyframe positions: exported, but not what the maps need)
         idx = torch.empty(M, dtype=torch.int64, device=dev)
         if M:
-            _lib.check(L.nvfi_render_export_masked(C.byref(desc), C.c_int64(R), C.c_float(T), C.c_int(flags), _lib.ptr(ws), C.c_int64(ws.numel()),
-                                                   C.c_int64(M), _lib.ptr(xw), _lib.ptr(idx), _stream_ptr()))
+            _lib.check(L.nvfi_render_export_masked(C.byref(desc), R, T, flags, _lib.ptr(ws), ws.numel(),
+                                                   M, _lib.ptr(xw), _lib.ptr(idx), _stream_ptr()))
         ray, smp = idx // S, idx % S
         # sample_ray by hand (tensorf_base.py:290-314, eval mode): the un-warped positions at time t
         inside = bool(((f.aabb[0] <= o) & (o <= f.aabb[1])).any())

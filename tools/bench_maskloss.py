@@ -94,8 +94,8 @@ def main():
             xyz = torch.empty(M, 3, device="cuda")
             idx = torch.empty(M, dtype=torch.int64, device="cuda")
             Rl, tl, flags = f._last_call
-            _lib.check(_lib.lib().nvfi_render_export_masked(C.byref(desc), C.c_int64(R), C.c_float(tl), C.c_int(flags), _lib.ptr(f._last_ws),
-                                                            C.c_int64(f._last_ws.numel()), C.c_int64(M), _lib.ptr(xyz), _lib.ptr(idx), _lib.stream_ptr()))
+            _lib.check(_lib.lib().nvfi_render_export_masked(C.byref(desc), R, tl, flags, _lib.ptr(f._last_ws),
+                                                            f._last_ws.numel(), M, _lib.ptr(xyz), _lib.ptr(idx), _lib.stream_ptr()))
         finally:
             f.mask_field = None
         q = torch.zeros(R, K, device="cuda").index_add(0, idx // w.shape[1], w.reshape(-1)[idx][:, None] * mf(xyz))
