@@ -487,6 +487,10 @@ int nvfi_advect_grad(const nvfi_field_desc* f, int64_t N, const float* x, float 
                      const float* g_xk /* (N,3) */, float* g_x /* (N,3) or NULL, WRITTEN */,
                      const nvfi_grads* grads /* vW / vb ACCUMULATED, the rest ignored */,
                      void* workspace, int64_t workspace_bytes, void* stream);
+/* differentiable advection with PER-POINT times (nvfi_advect_pt_steps, nvfi_advect_grad_pt_workspace_bytes, nvfi_advect_grad_pt): declared in
+ * nvfi_hip_advect_pt.h, which this line brings in - part of this header for every C consumer.  The prototype list of THIS file is the one
+ * nvfi_amd/_lib.py: SIGNATURES restates row by row; additions behind it live in headers of their own, with their rows in _lib.ADDITIONS. */
+#include "nvfi_hip_advect_pt.h"
 /* compute_densityfeature + feature2density (tensorf_keyframe.py:233-272, 312-321): xyzt (N,4) -> feat (N), sigma (N).
  * Errors (2), before anything is launched: an unsupported descriptor, N >= 2^31 - 256 (chunk the points). */
 int nvfi_density_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, float* feat, float* sigma, void* stream);

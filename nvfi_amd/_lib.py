@@ -145,6 +145,15 @@ SIGNATURES = {
     "nvfi_selftest": "pp",
 }
 EXPORTS = list(SIGNATURES)
+# The prototypes of the headers include/nvfi_hip.h brings in behind its own list, same letters: header -> rows in the header's order.  lib() binds
+# them exactly like SIGNATURES; tests/test_advect_pt_abi.py holds the rows against include/nvfi_hip_advect_pt.h.
+ADDITIONS = {
+    "nvfi_hip_advect_pt.h": {
+        "nvfi_advect_pt_steps": "plppppp",
+        "nvfi_advect_grad_pt_workspace_bytes": "plip",
+        "nvfi_advect_grad_pt": "plpppippppplp",
+    },
+}
 
 _LIB = None
 
@@ -161,8 +170,9 @@ def lib():
             raise NvfiError(f"{SO} is missing: build it with `python -m nvfi_amd.build` (needs hipcc). "
                             "There is no CPU fallback for the NVFi hot path.")
         L = C.CDLL(SO)
-        for name, kinds in SIGNATURES.items():      # getattr raises AttributeError on a missing symbol
-            getattr(L, name).argtypes = [KINDS[k] for k in kinds]
+        for table in [SIGNATURES] + list(ADDITIONS.values()):
+            for name, kinds in table.items():       # getattr raises AttributeError on a missing symbol
+                getattr(L, name).argtypes = [KINDS[k] for k in kinds]
         L.nvfi_last_error.restype = C.c_char_p      # every other function returns int, ctypes' default
         if L.nvfi_abi_version() != ABI_VERSION:
             raise NvfiError(f"{SO} has ABI version {L.nvfi_abi_version()}, this binding is written for {ABI_VERSION}: rebuild it "

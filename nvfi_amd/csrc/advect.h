@@ -18,5 +18,8 @@ void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKind kind,
 // advected positions), P.list (the identity) and P.count[0] (the DEVICE count of points, <= N): the weight images, the stash-writing uniform
 // warp, the unfused adjoint (which stores the gradient at the start into g_x when that is not NULL) and the six weight-gradient jobs,
 // ACCUMULATED into grads->vW / vb.  N is the launch capacity; nsteps >= 1.
+// pt_dt / pt_tc (advect_pt.hip; then dts / tcs are not read): a device-side schedule table, dt[s][i] / tcur[s][i] for s < nsteps and i the
+// index in P.list, N apart - every point takes its own steps, one with dt == 0 at a step rests there (the per-point-times kernels of
+// vel_x6.hip / vel_split.hip).
 int advect_chain(const nvfi_field_desc* f, const AdvectPlan& P, int64_t N, int nsteps, const float* dts, const float* tcs, WarpKind kind,
-                 float* g_x, const nvfi_grads* grads, hipStream_t st);
+                 float* g_x, const nvfi_grads* grads, hipStream_t st, const float* pt_dt = nullptr, const float* pt_tc = nullptr);

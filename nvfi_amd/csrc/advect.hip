@@ -9,7 +9,8 @@
 //   launch_rk2_split_bwd(gx0)                      k_rk2_split_bwd<true>: the unfused adjoint, which also stores the gradient at the start
 //   launch_vel_wgrad(fused_nslab = 0)              six ring jobs + the slab reduce, ACCUMULATED into grads->vW / vb
 // The adjoint is always the unfused pair, whatever NVFI_RK2_FUSE says: the fused kernel (vel_fuse.hip) has no position output.
-// Everything behind the pack kernel is advect_chain (advect.h), the host-side entry nvfi_flow_loss_bwd (flowloss.hip) shares.
+// Everything behind the pack kernel is advect_chain (advect.h), the host-side entry nvfi_flow_loss_bwd (flowloss.hip) and nvfi_advect_grad_pt
+// (advect_pt.hip: per-point times, the same chain on a device-side schedule table) share.
 // All on the caller's stream, no host synchronisation.
 #include <string.h>
 #include "common.h"
@@ -108,25 +109,27 @@ extern "C" int nvfi_advect_grad(const nvfi_field_desc* f, int64_t N, const float
 
 // the launches behind the caller's pack kernel (advect.h): shared with nvfi_flow_loss_bwd (flowloss.hip)
 int advect_chain(const nvfi_field_desc* f, const AdvectPlan& P, int64_t N, int nsteps, const float* dts, const float* tcs, WarpKind kind,
-                 float* g_x, const nvfi_grads* grads, hipStream_t st) {
+                 float* g_x, const nvfi_grads* grads, hipStream_t st, const float* pt_dt, const float* pt_tc) {
+    const bool pt = pt_dt != nullptr;
     VelImages VI;
     const unsigned need = VI_VEL | VI_X4B | (kind == WARP_X6 ? VI_X6 : VI_X4F);
     if (int rc = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, nullptr}, &VI, nullptr, 0, st)) return rc;
     Rk2Args ra; memset(&ra, 0, sizeof(ra));
     ra.f = *f; ra.Wv = VI.VW; ra.count = P.count; ra.list = P.list; ra.xw = P.xw; ra.xout = nullptr;
     ra.nsteps = nsteps; ra.sched = nullptr;
-    for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
+    if (pt) { ra.pt_t = pt_dt; ra.pt_base = pt_tc; }
+    else for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
     ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles; ra.z_x4 = 0; ra.gxk = P.gxk;
     if (kind == WARP_X6) {
         X6UniArgs xa; xa.r = ra; xa.img = VI.x6;
-        if (launch_rk2_x6_uni(xa, N, true, st)) return 1;
+        if (pt ? launch_rk2_x6_uni_pt(xa, N, st) : launch_rk2_x6_uni(xa, N, true, st)) return 1;
     } else {
         SplitUniArgs ua; ua.r = ra;
         for (int l = 0; l < 6; ++l) { ua.f4[l] = VI.f4[l]; ua.bv[l] = VI.VW.b[l]; }
-        if (launch_rk2_split_uni(ua, N, true, st)) return 1;
+        if (pt ? launch_rk2_split_uni_pt(ua, N, st) : launch_rk2_split_uni(ua, N, true, st)) return 1;
     }
     SplitBwdArgs ba; ba.r = ra; ba.gx0 = g_x;
     for (int l = 0; l < 6; ++l) ba.t4[l] = VI.t4[l];
-    if (launch_rk2_split_bwd(ba, N, st, true)) return 1;
+    if (pt ? launch_rk2_split_bwd_pt(ba, N, st) : launch_rk2_split_bwd(ba, N, st, true)) return 1;
     return launch_vel_wgrad(P.zst, P.x0st, P.gst, P.count, (int)P.cap_tiles, 2 * nsteps, BM_SILU, P.slabs, ADV_NSLAB, grads->vW, grads->vb, 1.f, st, 0);
 }

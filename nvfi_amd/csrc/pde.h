@@ -104,6 +104,10 @@ int launch_rk2_split_uni(const SplitUniArgs& a, int64_t cap_samples, bool stash,
 // instantiation alone (want_gx0: nvfi_advect_grad, advect.hip); the render launches the plain one and leaves it NULL
 struct SplitBwdArgs { Rk2Args r; const float4* t4[6]; float* gx0 = nullptr; };
 int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st, bool want_gx0 = false);
+// the stash-writing warp and its adjoint with per-point times (advect_pt.hip): Rk2Args::pt_t / pt_base hold the schedule table, dt[s][i] /
+// tcur[s][i] with i the compact index, r.cap apart; r.nsteps steps, a sample with dt == 0 at a step rests there
+int launch_rk2_split_uni_pt(const SplitUniArgs& a, int64_t cap_samples, hipStream_t st);
+int launch_rk2_split_bwd_pt(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st);
 
 // opt-in fp16 pre-pass of the prefilter (pre16.hip)
 #define PRE16_IMAGE_BYTES 150528   // fp16 fragments of the six weight_net layers (144 KB) + fp32 biases: staged into LDS once per workgroup

@@ -32,6 +32,8 @@ struct Rk2Args {
     // per-point mode
     const float* pt_t; const float* pt_base; float dt_max; int max_steps;
     int pt_by_list;        // pt_t / pt_base are indexed by the dense index list[i] instead of the compact index i
+    // (the stash kernels with per-point times - k_rk2_x6_uni_pt, k_rk2_split_uni<., true>, k_rk2_split_bwd<., true> - read pt_t / pt_base as the
+    // schedule table of advect_pt.hip instead: dt[s][i] / tcur[s][i], i the compact index, `cap` apart, nsteps steps)
     // stashes (training)
     float* zst; float* x0st; float* rec; float* gst;
     int64_t cap; int64_t cap_tiles;
@@ -48,9 +50,9 @@ struct Rk2Args {
 //   rk2_record_store                      k_rk2_split_uni<true>
 //   vel_stage_biases / vel_stage_w5       k_rk2_split, k_rk2_split_uni / k_rk2_split
 // These are NOT the only copies.  The same statements are still written out, and have to be kept in step BY HAND with a change made here, in:
-//   the two halves of a step (gate, half step, full step, gate_sur rejection): vel.hip k_rk2_fwd; vel_x6.hip k_rk2_x6, k_rk2_x6_uni;
+//   the two halves of a step (gate, half step, full step, gate_sur rejection): vel.hip k_rk2_fwd; vel_x6.hip k_rk2_x6, k_rk2_x6_uni, k_rk2_x6_uni_pt;
 //       vel_x6w.hip k_rk2_x6w, k_rk2_x6w_uni; pre16.hip k_rk2_pre16, k_rk2_inf16
-//   the record store (RK_NF fields, flags last): vel_x6.hip k_rk2_x6_uni; vel_x6w.hip k_rk2_x6w_uni; pre16.hip k_rk2_inf16; its readers are
+//   the record store (RK_NF fields, flags last): vel_x6.hip k_rk2_x6_uni, k_rk2_x6_uni_pt; vel_x6w.hip k_rk2_x6w_uni; pre16.hip k_rk2_inf16; its readers are
 //       k_rk2_split_bwd (vel_split.hip) and vel_fuse.hip
 //   the bias / output-weight staging: vel_x6.hip (both kernels), vel_x6w.hip (both kernels)
 // Why: calling the helpers there changed the compiled instructions.  vel_x6.hip, vel_x6w.hip and pre16.hip lie behind the packed-fp32 fence

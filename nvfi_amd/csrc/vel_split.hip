@@ -252,7 +252,9 @@ __global__ __launch_bounds__(WG_THREADS, SPLIT_WG_PER_CU_1) void k_rk2_split(Spl
 // step, 0.59 -> 0.63 of the fp32 MFMA peak), but the allocator then takes 228 / 204 registers instead of 179 / 150, the gather / scatter
 // kernels of the other chains no longer fit beside its two waves per SIMD, and the three-stream step gains nothing (5.04 against 5.07 ms)
 #define SPLIT_UNI_LDS_BYTES (SPLIT_NT * (SPLIT_XCH_F4 * 16 + 4 * 64 * 4) + 6 * 128 * 4)
-template <bool STASH>
+// PT (nvfi_advect_grad_pt, advect_pt.hip): every sample reads its own (dt, start time) of step s from the schedule table ra.pt_t / ra.pt_base
+// ([s][compact index], ra.cap apart); a sample whose dt is 0 there has finished: the step leaves it where it is and records flag 4
+template <bool STASH, bool PT = false>
 __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_uni(SplitUniArgs a) {
     constexpr int NT = SPLIT_NT;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -281,7 +283,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_uni(SplitUniArgs a)
     __syncthreads();
 #pragma unroll 1
     for (int s = 0; s < ra.nsteps; ++s) {
-        const float dt = RK_DT(ra, s), tcur = RK_TC(ra, s), hdt = 0.5f * dt;
+        const float dt = PT ? 0.f : RK_DT(ra, s), tcur = PT ? 0.f : RK_TC(ra, s), hdt = 0.5f * dt;
+        float dtp[NT], tcp[NT];
+        if constexpr (PT) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const size_t o = (size_t)s * ra.cap + (active[t] ? idx[t] : 0);
+                dtp[t] = active[t] ? ra.pt_t[o] : 0.f; tcp[t] = active[t] ? ra.pt_base[o] : 0.f;
+            }
+        }
         float* z1[NT]; float* z2[NT]; float* x1[NT]; float* x2[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -294,20 +304,20 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_uni(SplitUniArgs a)
         int g1[NT];
         float4 q[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) q[t] = make_float4(x[t], y[t], z[t], tcur);
+        for (int t = 0; t < NT; ++t) q[t] = make_float4(x[t], y[t], z[t], PT ? tcp[t] : tcur);
         velnet_split<STASH>(a.f4, xch, bc, w, owner, lane, h, q, wq, lb, o4, z1, x1);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             gather6(o4[t], h, w1[t]);
-            g1[t] = rk2_midpoint(ra.f, w1[t], x[t], y[t], z[t], hdt, px[t], py[t], pz[t]);
-            q[t] = make_float4(px[t], py[t], pz[t], tcur - hdt);
+            g1[t] = rk2_midpoint(ra.f, w1[t], x[t], y[t], z[t], PT ? 0.5f * dtp[t] : hdt, px[t], py[t], pz[t]);
+            q[t] = make_float4(px[t], py[t], pz[t], PT ? tcp[t] - 0.5f * dtp[t] : tcur - hdt);
         }
         velnet_split<STASH>(a.f4, xch, bc, w, owner, lane, h, q, wq, lb, o4, z2, x2);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             float w2[6], nx, ny, nz;
             gather6(o4[t], h, w2);
-            const int g2rej = rk2_final(ra.f, w2, x[t], y[t], z[t], px[t], py[t], pz[t], dt, nx, ny, nz);
+            const int g2rej = rk2_final(ra.f, w2, x[t], y[t], z[t], px[t], py[t], pz[t], PT ? dtp[t] : dt, nx, ny, nz) | (PT && dtp[t] == 0.f ? 4 : 0);
             if (STASH && active[t] && h == 0 && w == (t & 3))
                 rk2_record_store(ra.rec + (size_t)s * RK_NF * ra.cap + idx[t], ra.cap, x[t], y[t], z[t], px[t], py[t], pz[t], w1[t], w2, g1[t] | g2rej);
             if (active[t] && !(g2rej & 4)) { x[t] = nx; y[t] = ny; z[t] = nz; }
@@ -325,6 +335,17 @@ int launch_rk2_split_uni(const SplitUniArgs& a, int64_t cap_samples, bool stash,
     const dim3 g((unsigned)((tiles + SPLIT_NT - 1) / SPLIT_NT)), b(WG_THREADS);
     if (stash) hipLaunchKernelGGL(k_rk2_split_uni<true>, g, b, SPLIT_UNI_LDS_BYTES, st, a);
     else hipLaunchKernelGGL(k_rk2_split_uni<false>, g, b, SPLIT_UNI_LDS_BYTES, st, a);
+    LAUNCHCK();
+    return 0;
+}
+
+// the per-point-times stash form (nvfi_advect_grad_pt)
+int launch_rk2_split_uni_pt(const SplitUniArgs& a, int64_t cap_samples, hipStream_t st) {
+    const int64_t tiles = (cap_samples + TILE - 1) / TILE;
+    if (tiles <= 0) return 0;
+    ProfScope ps(PK_RK2_FWD, st);
+    const dim3 g((unsigned)((tiles + SPLIT_NT - 1) / SPLIT_NT)), b(WG_THREADS);
+    hipLaunchKernelGGL((k_rk2_split_uni<true, true>), g, b, SPLIT_UNI_LDS_BYTES, st, a);
     LAUNCHCK();
     return 0;
 }
@@ -414,7 +435,9 @@ __device__ __forceinline__ void velnet_split_bwd(const float4* const* t4, float4
 
 // GX0 (nvfi_advect_grad): the gradient that is left in g3 after the last (= first forward) step goes to a.gx0 - the one output the render never
 // needed, its samples being constants.  The render launches the plain instantiation
-template <bool GX0>
+// PT (nvfi_advect_grad_pt): dt and the start time of step s are the sample's own, from the table the PT forward read (ra.pt_t / ra.pt_base); a
+// finished sample's step carries record flag 4 and is the identity, like a rejected one
+template <bool GX0, bool PT = false>
 __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_bwd(SplitBwdArgs a) {
     constexpr int NT = SPLIT_NT;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -437,7 +460,15 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_bwd(SplitBwdArgs a)
     float4 wq[16];
 #pragma unroll 1
     for (int s = ra.nsteps - 1; s >= 0; --s) {
-        const float dt = RK_DT(ra, s), tcur = RK_TC(ra, s);
+        const float dt = PT ? 0.f : RK_DT(ra, s), tcur = PT ? 0.f : RK_TC(ra, s);
+        float dtp[NT], tcp[NT];
+        if constexpr (PT) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const size_t o = (size_t)s * ra.cap + (active[t] ? idx[t] : 0);
+                dtp[t] = active[t] ? ra.pt_t[o] : 0.f; tcp[t] = active[t] ? ra.pt_base[o] : 0.f;
+            }
+        }
         float gacc[NT][3], gup[NT][3];
         bool g1[NT], g2[NT], rej[NT];
 #pragma unroll
@@ -468,7 +499,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_bwd(SplitBwdArgs a)
                 for (int k = 0; k < 6; ++k) wv[k] = active[t] ? rc[(wo + k) * ra.cap] : 0.f;
                 const bool on = active[t] && !rej[t] && !gate;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) gv[c] = on ? coef * gup[t][c] : 0.f;
+                for (int c = 0; c < 3; ++c) gv[c] = on ? (PT ? (e ? -dtp[t] : -0.5f * dtp[t]) : coef) * gup[t][c] : 0.f;
                 gw[0] = gv[0]; gw[1] = gv[1]; gw[2] = gv[2];
                 gw[3] = p[2] * gv[1] - p[1] * gv[2];
                 gw[4] = -p[2] * gv[0] + p[0] * gv[2];
@@ -485,7 +516,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_split_bwd(SplitBwdArgs a)
                 float p[3], x0[16];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) p[c] = active[t] ? rc[(po + c) * ra.cap] : 0.f;
-                vel_encode_slots(make_float4(p[0], p[1], p[2], te), h, x0);
+                vel_encode_slots(make_float4(p[0], p[1], p[2], PT ? (e ? tcp[t] - 0.5f * dtp[t] : tcp[t]) : te), h, x0);
                 const float4 gq = vel_encode_bwd(ge[t], x0, h);
                 gloc[t][0] += gq.x; gloc[t][1] += gq.y; gloc[t][2] += gq.z;
 #pragma unroll
@@ -516,6 +547,18 @@ int launch_rk2_split_bwd(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t
     const dim3 g((unsigned)((tiles + SPLIT_NT - 1) / SPLIT_NT)), b(WG_THREADS);
     if (want_gx0 && a.gx0) hipLaunchKernelGGL(k_rk2_split_bwd<true>, g, b, SPLIT_BWD_LDS_BYTES, st, a);
     else hipLaunchKernelGGL(k_rk2_split_bwd<false>, g, b, SPLIT_BWD_LDS_BYTES, st, a);
+    LAUNCHCK();
+    return 0;
+}
+
+// the per-point-times adjoint (nvfi_advect_grad_pt); a.gx0 may be NULL
+int launch_rk2_split_bwd_pt(const SplitBwdArgs& a, int64_t cap_samples, hipStream_t st) {
+    const int64_t tiles = (cap_samples + TILE - 1) / TILE;
+    if (tiles <= 0) return 0;
+    ProfScope ps(PK_RK2_BWD, st);
+    const dim3 g((unsigned)((tiles + SPLIT_NT - 1) / SPLIT_NT)), b(WG_THREADS);
+    if (a.gx0) hipLaunchKernelGGL((k_rk2_split_bwd<true, true>), g, b, SPLIT_BWD_LDS_BYTES, st, a);
+    else hipLaunchKernelGGL((k_rk2_split_bwd<false, true>), g, b, SPLIT_BWD_LDS_BYTES, st, a);
     LAUNCHCK();
     return 0;
 }

@@ -415,6 +415,88 @@ int launch_rk2_x6_uni(const X6UniArgs& a, int64_t cap_samples, bool stash, hipSt
     return 0;
 }
 
+// ---------------------------------------------------------------- stash form with per-point times (nvfi_advect_grad_pt, advect_pt.hip)
+// k_rk2_x6_uni<1, true> written out once more, by the rule of vel.h (a template parameter on that kernel moved the register allocation of
+// its existing instantiations): same compact list, same stash rows, same RK_NF record, one tile per workgroup.  Every sample reads its own
+// (dt, start time) of step s from the schedule table ra.pt_t / ra.pt_base ([s][compact index], ra.cap apart; k_advect_pt_sched).  A sample
+// whose dt is 0 there has finished (a dead step): its state stays, the record carries flag 4 - the flag of a rejected step, which the adjoint
+// treats as the identity - and its stash rows are still written from the evaluations at the resting point, finite like any other.  Live steps
+// are k_rk2_x6's statements in k_rk2_x6's order, so the end point is nvfi_integrate_pos' bit for bit.
+__global__ __launch_bounds__(WG_THREADS, 2) void k_rk2_x6_uni_pt(X6UniArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    b8_t* xch = reinterpret_cast<b8_t*>(lds);
+    float4* part = reinterpret_cast<float4*>(xch + X6_XCH_H8);
+    const Rk2Args& ra = a.r;
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int count = *ra.count;
+    if ((int)blockIdx.x * TILE >= (count + WG_SAMPLES - 1) / WG_SAMPLES * WG_SAMPLES) return;
+    const int idx = blockIdx.x * TILE + (lane & 31);
+    const bool active = idx < count;
+    const int n = active ? ra.list[idx] : 0;
+    const float4 q0 = active ? ra.xw[n] : zero4();
+    float x = q0.x, y = q0.y, z = q0.z;
+    float* lb = reinterpret_cast<float*>(part + 4 * 2 * 32);
+    for (int k = threadIdx.x; k < 6 * 128; k += WG_THREADS) lb[k] = (k & 127) < (k < 640 ? 128 : 6) ? ra.f.vb[k >> 7][k & 127] : 0.f;
+    float* w5f = lb + 6 * 128;
+    for (int k = threadIdx.x; k < 4 * 2 * 16 * 8; k += WG_THREADS) {
+        const int o = k & 7, r = (k >> 3) & 15, hh = (k >> 7) & 1, ww = k >> 8;
+        w5f[k] = o < 6 ? ra.f.vW[5][o * 128 + 32 * ww + (r & 3) + 8 * (r >> 2) + 4 * hh] : 0.f;
+    }
+    const float4* w5l = reinterpret_cast<const float4*>(w5f);
+    const b8_t* img = reinterpret_cast<const b8_t*>(a.img);
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < ra.nsteps; ++s) {
+        const size_t so = (size_t)s * ra.cap + (active ? idx : 0);
+        const float dt = active ? ra.pt_t[so] : 0.f, tcur = active ? ra.pt_base[so] : 0.f, hdt = 0.5f * dt;
+        const size_t tile = blockIdx.x;
+        const size_t e1 = (size_t)(2 * s) * ra.cap_tiles + tile, e2 = (size_t)(2 * s + 1) * ra.cap_tiles + tile;
+        float* z1[1] = {ra.zst + e1 * (VEL_Z_REGS * REGF)}; float* z2[1] = {ra.zst + e2 * (VEL_Z_REGS * REGF)};
+        float* x1[1] = {ra.x0st + e1 * (VEL_X0_REGS * REGF)}; float* x2[1] = {ra.x0st + e2 * (VEL_X0_REGS * REGF)};
+        float o6[1][6], w1[6], v1[3], v2[3];
+        float4 q[1];
+        q[0] = make_float4(x, y, z, tcur);
+        velnet_x6<1, true, false>(img, xch, part, w5l, w, lane, h, q, lb, o6, z1, x1);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) w1[k] = o6[0][k];
+        vel_from_w(w1, x, y, z, v1);
+        const bool g1 = gated_out(ra.f, x, y, z);
+        if (g1) { v1[0] = v1[1] = v1[2] = 0.f; }
+        const float px = x - hdt * v1[0], py = y - hdt * v1[1], pz = z - hdt * v1[2];
+        q[0] = make_float4(px, py, pz, tcur - hdt);
+        velnet_x6<1, true, false>(img, xch, part, w5l, w, lane, h, q, lb, o6, z2, x2);
+        const float* w2 = o6[0];
+        vel_from_w(w2, px, py, pz, v2);
+        const bool g2 = gated_out(ra.f, px, py, pz);
+        if (g2) { v2[0] = v2[1] = v2[2] = 0.f; }
+        const float nx = x - dt * v2[0], ny = y - dt * v2[1], nz = z - dt * v2[2];
+        const bool rej = (ra.f.gate_sur && gated_out(ra.f, nx, ny, nz)) || dt == 0.f;   // tensorf_keyframe.py:603-605, or a dead step
+        if (active && h == 0 && w == 0) {
+            float* rc = ra.rec + (size_t)s * RK_NF * ra.cap + idx;
+            rc[0 * ra.cap] = x; rc[1 * ra.cap] = y; rc[2 * ra.cap] = z;
+            rc[3 * ra.cap] = px; rc[4 * ra.cap] = py; rc[5 * ra.cap] = pz;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { rc[(6 + k) * ra.cap] = w1[k]; rc[(12 + k) * ra.cap] = w2[k]; }
+            rc[18 * ra.cap] = __int_as_float((g1 ? 1 : 0) | (g2 ? 2 : 0) | (rej ? 4 : 0));
+        }
+        if (active && !rej) { x = nx; y = ny; z = nz; }
+    }
+    if (active && h == 0 && w == 0) ra.xw[n] = make_float4(x, y, z, q0.w);
+}
+
+// always this kernel: NVFI_X6W_UNI does not apply, vel_x6w.hip has no such form
+int launch_rk2_x6_uni_pt(const X6UniArgs& a, int64_t cap_samples, hipStream_t st) {
+    const int64_t tiles = (cap_samples + TILE - 1) / TILE;
+    if (tiles <= 0) return 0;
+    static DeviceOnce once;
+    if (once.lds(X6_LDS_BYTES(1), k_rk2_x6_uni_pt)) return 1;
+    ProfScope ps(PK_RK2_FWD, st);
+    hipLaunchKernelGGL(k_rk2_x6_uni_pt, dim3((unsigned)tiles), dim3(WG_THREADS), X6_LDS_BYTES(1), st, a);
+    LAUNCHCK();
+    return 0;
+}
+
 int launch_rk2_x6(const X6Args& a, int64_t cap_points, hipStream_t st) {
     const int64_t tiles = (cap_points + TILE - 1) / TILE;
     if (tiles <= 0) return 0;

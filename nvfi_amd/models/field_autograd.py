@@ -326,6 +326,83 @@ class _AdvectFn(torch.autograd.Function):
         return (None, gx, None, None, None) + tuple(grads)
 
 
+class _AdvectPtFn(torch.autograd.Function):
+    """autograd boundary around nvfi_integrate_pos / nvfi_advect_grad_pt (include/nvfi_hip_advect_pt.h) for per-point times, built like _AdvectFn.  The
+    forward IS field.integrate_pos; it also runs nvfi_advect_pt_steps and reads the 66-bin histogram of the step counts - THE ONE HOST
+    SYNCHRONISATION of the call (a point beyond 64 steps is refused here, before anything else, and the backward plans from the histogram
+    alone).  The backward's cost follows the sum of the steps, not N x the largest: the points are sorted by step count (descending, stable),
+    every step count is planned on its own with `_lib.plan_chunks` under `max_ws` bytes and launched with that count as its max_steps, and
+    the zero-step tail launches nothing (g_x = g there).  The times get no gradient."""
+    N_ARGS = 5      # field, x, t, t_target, max_ws
+
+    @staticmethod
+    def forward(ctx, field, x, t, t_target, max_ws, *params):
+        L = _lib.lib()
+        N = x.shape[0]
+        desc = field._desc()
+        steps = torch.empty(N, dtype=torch.int32, device=x.device)
+        hist = torch.empty(66, dtype=torch.int64, device=x.device)
+        _lib.check(L.nvfi_advect_pt_steps(C.byref(desc), N, _lib.ptr(t), _lib.ptr(t_target), _lib.ptr(steps), _lib.ptr(hist), _stream_ptr()))
+        hist = hist.tolist()                     # the host read
+        if hist[65]:
+            raise _lib.NvfiError(f"libnvfi_hip error 2: advect_pt: {hist[65]} point(s) need more than 64 RK2 steps (refused, not truncated)")
+        xk = field.integrate_pos(x, t, t_target)
+        ctx.field, ctx.max_ws, ctx.hist = field, int(max_ws), hist[:65]
+        ctx.save_for_backward(x, t, t_target, steps, *params)
+        ctx.set_materialize_grads(False)
+        return xk
+
+    @staticmethod
+    def plan(nbytes, hist, max_ws):
+        """[(first, n, max_steps)] over the points sorted by step count, descending, and the bytes of the largest chunk: one plan_chunks per
+        step count that occurs; the zero-step points come last as one entry that launches nothing"""
+        chunks, first, ws_bytes = [], 0, 0
+        for s in range(len(hist) - 1, 0, -1):
+            if not hist[s]:
+                continue
+            chunk, nb, _ = _lib.plan_chunks(lambda n: nbytes(n, s), hist[s], max_ws, "advect_pt", unit="point")
+            ws_bytes = max(ws_bytes, nb)
+            for i in range(0, hist[s], chunk):
+                chunks.append((first + i, min(chunk, hist[s] - i), s))
+            first += hist[s]
+        if hist[0]:
+            chunks.append((first, hist[0], 0))
+        return chunks, ws_bytes
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, t, t1, steps, *params = ctx.saved_tensors
+        if g is None:
+            return (None,) * (_AdvectPtFn.N_ARGS + len(params))
+        L = _lib.lib()
+        field = ctx.field
+        desc = field._desc(field._params_with(fs.WEIGHT_NET, params))
+        grads, G = _plain_grads(field, params, ctx.needs_input_grad[_AdvectPtFn.N_ARGS:], fs.PDE_WEIGHT_NET, vel=True)
+        g = g.reshape(-1, 3).contiguous().float()
+        want_gx = ctx.needs_input_grad[1]
+        chunks, ws_bytes = _AdvectPtFn.plan(lambda n, s: _lib.bytes_of(L.nvfi_advect_grad_pt_workspace_bytes, C.byref(desc), n, s), ctx.hist, ctx.max_ws)
+        field.last_advect_pt_chunks = [(n, s) for _, n, s in chunks]
+        field.last_advect_pt_workspace_bytes = ws_bytes
+        if not any(s for _, _, s in chunks):      # nobody moves: the gradient passes through, the net gets exact zeros
+            return (None, g.clone() if want_gx else None, None, None, None) + tuple(grads)
+        order = torch.argsort(steps, descending=True, stable=True)
+        xs, ts, t1s, gs = x[order], t[order], t1[order], g[order]
+        gxs = gs.clone() if want_gx else None     # the zero-step tail keeps g
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        for i, n, s in chunks:
+            if s == 0:
+                continue
+            _lib.check(L.nvfi_advect_grad_pt(C.byref(desc), n, _lib.ptr(xs[i:i + n]), _lib.ptr(ts[i:i + n]), _lib.ptr(t1s[i:i + n]), s,
+                                             _lib.ptr(gs[i:i + n]), None if gxs is None else _lib.ptr(gxs[i:i + n]), C.byref(G), None,
+                                             _lib.ptr(ws), ws.numel(), _stream_ptr()))
+        gx = None
+        if want_gx:
+            gx = torch.empty_like(gxs)
+            gx[order] = gxs
+        return (None, gx, None, None, None) + tuple(grads)
+
+
 class _ShadeFn(torch.autograd.Function):
     """autograd boundary around nvfi_render_mlp / nvfi_render_mlp_grad (include/nvfi_hip.h), built like _AdvectFn.  The forward IS
     field._render_module_call and saves only the three inputs and the six tensors of renderModule.mlp (none under SH shading): the backward

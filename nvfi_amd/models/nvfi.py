@@ -55,6 +55,10 @@ class NVFi(nn.Module):
         """integrate_pos(pos, t, t_target) with gradients to `pos` and the velocity net (TensorVMKeyframeTimeKplane.advect)"""
         return self.nvfi.advect(pos, t, t_target, max_workspace_bytes=max_workspace_bytes)
 
+    def advect_pt(self, pos, t, t_target, max_workspace_bytes=1 << 30):
+        """`advect` with per-point times: `t` / `t_target` a float or a device tensor of N elements each (TensorVMKeyframeTimeKplane.advect_pt)"""
+        return self.nvfi.advect_pt(pos, t, t_target, max_workspace_bytes=max_workspace_bytes)
+
     def lookup_density(self, xyzt):
         """compute_densityfeature with gradients to the points and the density planes (TensorVMKeyframeTimeKplane.lookup_density)"""
         return self.nvfi.lookup_density(xyzt)

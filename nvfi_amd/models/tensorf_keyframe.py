@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from .. import _lib
 from .._lib import stream_ptr as _stream_ptr
 from . import field_slots as fs
-from .field_autograd import _AdvectFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _MaskLossFn, _PdeFn, _RegFn, _RenderFn, _ShadeFn
+from .field_autograd import _AdvectFn, _AdvectPtFn, _AppLookupFn, _CharFn, _DensityLookupFn, _FlowLossFn, _MaskLossFn, _PdeFn, _RegFn, _RenderFn, _ShadeFn
 from .field_grads import FieldGrads, _rt, round64
 from .mask_field import _mask_desc
 from .tensorf_model_utils import AlphaGridMask
@@ -742,7 +742,8 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
         ts, t1s = scalar(t), scalar(t_target)
         if ts is None or t1s is None:
             if wants:
-                raise NotImplementedError("advect: per-point times (a tensor t / t_target with more than one distinct value) have no gradient path")
+                raise NotImplementedError("advect: per-point times (a tensor t / t_target with more than one distinct value) have no gradient path "
+                                          "here: use advect_pt")
             return self.integrate_pos(pos, t, t_target).reshape(pos.shape)
         desc = self._desc()
         if wants and (desc.vel_fp16 & 3) in (1, 2):
@@ -754,6 +755,46 @@ class TensorVMKeyframeTimeKplane(FieldGrads, nn.Module):
             tt = torch.full((x.shape[0],), ts, dtype=torch.float32, device=x.device)
             return self.integrate_pos(x, tt, torch.full_like(tt, t1s)).reshape(pos.shape)
         return _AdvectFn.apply(self, x, ts, t1s, int(max_workspace_bytes), *wparams).reshape(pos.shape)
+
+    def advect_pt(self, pos, t, t_target, max_workspace_bytes=1 << 30):
+        """`advect` with PER-POINT times: integrate_pos(pos_i, t_i, t_target_i) WITH gradients to `pos` and the 12 tensors of vel_net.weight_net,
+        for tracks that start at many frame times, random time pairs, points of all frames warped to their own keyframe - one call instead of
+        one `advect` per distinct pair.  `t` and `t_target` are each a Python float or a device tensor of N / (N,1) elements.  The times carry
+        NO gradient: a time tensor that requires grad is refused.  Every rule of `advect` holds (decisions held fixed, no second-order gradients,
+        the value is integrate_pos' bit for bit, vel_fp16 modes 1 / 2 have no adjoint).  A point more than 64 RK2 steps from its target is
+        refused (NvfiError, error 2) before anything is launched, not truncated.
+        ONE HOST SYNCHRONISATION per call with gradients: the forward reads the 66-bin histogram of the points' step counts (so the call cannot
+        be captured in a hipGraph).  The backward sorts the points by step count and runs every step count as chunks of its own, each under
+        `max_workspace_bytes`, so its cost follows the sum of the steps; zero-step points launch nothing.  `last_advect_pt_chunks` is the list of
+        (points, max_steps) it ran, `last_advect_pt_workspace_bytes` the workspace it took; the gradient comes back in the caller's order.
+        Under no_grad, or when neither `pos` nor a weight_net parameter requires grad, this is exactly integrate_pos."""
+        for name, v in (("t", t), ("t_target", t_target)):
+            if isinstance(v, torch.Tensor) and v.requires_grad:
+                raise _lib.NvfiError(f"advect_pt: {name} requires grad, but the times get no gradient (detach it)")
+        if not (isinstance(pos, torch.Tensor) and pos.is_cuda):
+            raise _lib.NvfiError("advect_pt needs its points on the GPU (no CPU fallback exists)")
+        if not self.use_vel:
+            raise _lib.NvfiError("advect_pt needs a field with a velocity net (use_vel)")
+        x = pos.reshape(-1, 3).contiguous().float()
+        N = x.shape[0]
+
+        def times(v, name):
+            if isinstance(v, torch.Tensor):
+                if not v.is_cuda:
+                    raise _lib.NvfiError(f"advect_pt needs {name} on the GPU (no CPU fallback exists)")
+                if v.numel() != N:
+                    raise _lib.NvfiError(f"advect_pt: {name} has {v.numel()} elements for {N} points")
+                return v.detach().reshape(-1).contiguous().float()
+            return torch.full((N,), float(v), dtype=torch.float32, device=x.device)
+
+        tt, t1 = times(t, "t"), times(t_target, "t_target")
+        wparams = self._render_params()[fs.WEIGHT_NET]
+        wants = torch.is_grad_enabled() and (pos.requires_grad or any(p.requires_grad for p in wparams))
+        if not wants:
+            return self.integrate_pos(x, tt, t1).reshape(pos.shape)
+        if (self._desc().vel_fp16 & 3) in (1, 2):
+            raise NotImplementedError("advect_pt: the fp16-input modes (vel_fp16 1 / 2) have no adjoint")
+        return _AdvectPtFn.apply(self, x, tt, t1, int(max_workspace_bytes), *wparams).reshape(pos.shape)
 
     @torch.no_grad()
     def compute_densityfeature(self, xyzt):
