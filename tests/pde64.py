@@ -63,21 +63,22 @@ def _chunk_terms(q, params):
     return div * div, (tr * tr).sum(-1), J
 
 
-def as_params(tensors, device="cpu"):
-    return [torch.as_tensor(np.asarray(p) if not isinstance(p, torch.Tensor) else p.detach().cpu()).to(device=device, dtype=torch.float64)
+def as_params(tensors, device="cpu", dtype=torch.float64):
+    return [torch.as_tensor(np.asarray(p) if not isinstance(p, torch.Tensor) else p.detach().cpu()).to(device=device, dtype=dtype)
             for p in tensors]
 
 
-def pde_sums(xn, t, params, idx=None, n_jac=0, grads=True, chunk=32768):
+def pde_sums(xn, t, params, idx=None, n_jac=0, grads=True, chunk=32768, acc_dtype=torch.float64):
     """UN-normalised sums over the points `idx` (default: all rows) of xn (P, 3) normalised coordinates and t (P,):
     S = 5 sum(div^2) + (0.1 / 3) sum(|transport|^2), sum(div^2), sum(|transport|^2), the gradients of S (24 float64 tensors) and the Jacobian
-    rows 0-2 of the first n_jac points.  The PDE loss of a kept set of n points is S / n, its gradients dS / n."""
+    rows 0-2 of the first n_jac points.  The PDE loss of a kept set of n points is S / n, its gradients dS / n.  The arithmetic runs in the
+    parameters' dtype (as_params: float64; float32 is the plain fp32 evaluation of the same statement); the chunks are summed in acc_dtype."""
     device = params[0].device
-    q_all = torch.cat([torch.as_tensor(xn).reshape(-1, 3), torch.as_tensor(t).reshape(-1, 1)], 1).to(device=device, dtype=torch.float64)
+    q_all = torch.cat([torch.as_tensor(xn).reshape(-1, 3), torch.as_tensor(t).reshape(-1, 1)], 1).to(device=device, dtype=params[0].dtype)
     if idx is not None:
         q_all = q_all[torch.as_tensor(np.asarray(idx), device=device, dtype=torch.long)]
     ps = [p.detach().clone().requires_grad_(grads) for p in params]
-    g = [torch.zeros_like(p) for p in ps]
+    g = [torch.zeros_like(p, dtype=acc_dtype) for p in ps]      # (acc_dtype float32: a plain fp32 sum over the chunks, one rounding per chunk)
     sd = st = 0.0
     jac = []
     for s in range(0, q_all.shape[0], chunk):
@@ -86,16 +87,16 @@ def pde_sums(xn, t, params, idx=None, n_jac=0, grads=True, chunk=32768):
             a, b = d2.sum(), t2.sum()
             if grads:
                 for acc, gi in zip(g, torch.autograd.grad(DIV_W * a + TR_W / 3.0 * b, ps)):
-                    acc += gi
+                    acc += gi.to(acc_dtype)
         sd += float(a.detach()); st += float(b.detach())
         if s < n_jac:
             jac.append(J[: n_jac - s].detach())
     jac = torch.cat(jac).cpu().numpy() if jac else np.zeros((0, 3, 4))
-    return dict(S=DIV_W * sd + TR_W / 3.0 * st, sum_div2=sd, sum_tr2=st, grads=[x.cpu().numpy() for x in g] if grads else None, jac=jac,
+    return dict(S=DIV_W * sd + TR_W / 3.0 * st, sum_div2=sd, sum_tr2=st, grads=[x.to(torch.float64).cpu().numpy() for x in g] if grads else None, jac=jac,
                 n=int(q_all.shape[0]))
 
 
-def pde64(points, t, kept, params, aabb, n_jac=0, grads=True, chunk=32768):
+def pde64(points, t, kept, params, aabb, n_jac=0, grads=True, chunk=32768, acc_dtype=torch.float64):
     """get_vel_loss in float64 on the kept set `kept` (bool (P,)) of world-space points (P, 3) and raw times (P,) / (P, 1).
     params: the 24 tensors (any device; the arithmetic runs on params[0]'s device after conversion, see as_params).
     Returns dict(loss, n_kept, jac (n_jac, 3, 4), grads: {name: float64 array}, sums: pde_sums of the kept set)."""
@@ -105,7 +106,7 @@ def pde64(points, t, kept, params, aabb, n_jac=0, grads=True, chunk=32768):
     n = len(idx)
     if n == 0:
         return dict(loss=0.0, n_kept=0, jac=np.zeros((0, 3, 4)), grads=None, sums=None, xn=xn, t=t, idx=idx)
-    s = pde_sums(xn, t, params, idx, n_jac, grads, chunk)
+    s = pde_sums(xn, t, params, idx, n_jac, grads, chunk, acc_dtype)
     out = dict(loss=s["S"] / n, n_kept=n, jac=s["jac"], sums=s, xn=xn, t=t, idx=idx)
     out["grads"] = {k: gk / n for k, gk in zip(NAMES, s["grads"])} if grads else None
     return out

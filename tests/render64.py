@@ -28,7 +28,7 @@ membership on the fp32 positions, the velocity gate and step rejection on the fp
 weight in `dtype` against float32(thres) - or GIVEN (`app_mask`: the device's own, read off its weight map), in which case the samples where the
 given mask and the yardstick's differ are reported with their |w - thres|.
 
-Rays are independent: they are processed in chunks, and the gradients accumulate over the chunks in float64.  The loss has to be a sum over rays:
+Rays are independent: they are processed in chunks, and the gradients accumulate over the chunks in float64 (acc_dtype: in another dtype).  The loss has to be a sum over rays:
 a `Loss` (mse + w_depth mean(depth) + w_acc mean(acc^2) + sum(weight gw): the golden loss; w_depth = w_acc = 0 and no gw is the bench's mse) or a
 callable (rgb, depth, acc, weight, ray_index, R) -> per-ray terms.
 
@@ -140,6 +140,10 @@ def sample_rays(field, rays_o, rays_d, jitter):
 def time_plan(field, t, transfer=False):
     """the base time, the keyframe decision and the RK2 schedule [(t_curr, dt), ...] of one call, computed in fp32 like the reference's tensors"""
     t32 = torch.tensor(float(t), dtype=torch.float32)
+    if not getattr(field, "use_vel", True):
+        # a radiance-only field (use_vel False, tensorf_keyframe.py:703-704): no warp, every lookup at the CONTINUOUS normalised frame time
+        tn = t32 * 0 if field.tmax == 0 else t32 * 2 / field.tmax - 1
+        return dict(base=float(t32), key=True, steps=[], tn_base=float(tn))
     scale = field.tmax / (field.K - 1) if field.K > 1 else 1
     base = torch.zeros_like(t32) if transfer else torch.round((t32 / scale).clamp(0.0, field.K - 1)) * scale
     key = bool(torch.isclose(t32, base))
@@ -217,7 +221,7 @@ def _mlp_in(P, x4m, view):
 
 
 def _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None,
-           wrong=False):
+           wrong=False, kink=0.0):
     """one chunk of rays sl (index array): the maps, the masks, the per-ray loss terms (a tensor still attached to the graph)"""
     idx = torch.as_tensor(sl, dtype=torch.long)
     valid = smp["valid"][idx].to(device)
@@ -275,10 +279,14 @@ def _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, 
         for i in () if field.sh else (0, 2, 4):
             W, b = P[f"renderModule.mlp.{i}.weight"], P[f"renderModule.mlp.{i}.bias"]
             zz = F.linear(h, W, b)
-            if want_margin and i < 4:
+            if (want_margin or kink) and i < 4:
                 err = (F.linear(h.abs(), W.abs()) + b.abs()) * (2.0 ** -24 * h.shape[1])
+            if want_margin and i < 4:
                 margin = torch.minimum(margin, (zz.abs() / err).min(1).values).detach()
-            h = torch.relu(zz) if i < 4 else torch.sigmoid(zz)
+            if kink and i < 4:       # the ReLU DECISION taken `kink` rounding bounds beside the pre-activation (the value passed on is still zz)
+                h = torch.where((zz + kink * err).detach() > 0, zz, torch.zeros_like(zz))
+            else:
+                h = torch.relu(zz) if i < 4 else torch.sigmoid(zz)
         if cut_rgb is not None:
             cr = cut_rgb[idx].to(device).reshape(-1)[mi]
             h = torch.where(cr[:, None], h.detach(), h)
@@ -314,13 +322,18 @@ MAP_KEYS = ("rgb", "depth", "acc", "weight", "app_mask", "own_mask", "valid", "i
 
 def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=None, transfer=False, grads=True, rays=None, chunk=256,
              dtype=torch.float64, device="cpu", cut_rgb=None, cut_sigma=None, want_margin=False, cut_warp=None, alpha_volume=None, cull_flip=None,
-             wrong=False):
+             wrong=False, acc_dtype=torch.float64, kink=0.0):
     """the render of the rays `rays` (default: all; the sampling and the loss's 1 / R always refer to the full batch) -> dict of the maps (numpy),
     `loss_rays` (per-ray loss terms, float64), `loss` (their sum), `grads` {name: float64 array, or None where the parameter is not reached},
     `flips` (indices (ray, sample) where the given app_mask differs from the yardstick's own) and `flip_dist` (their |w - thres|).
     alpha_volume (D, H, W), eval calls only: the in-box samples whose occupancy read is not > 0 are culled; the result then holds `in_box` (R, S; the
     valid map before culling), `culled`, `alpha_near` (in-box samples whose decision may fall the other way, alpha64.sample_alpha64) over ALL rays of
-    the batch; cull_flip: (n, 2) (ray, sample) whose culling decision is inverted (what a wrong lookup would do to them)"""
+    the batch; cull_flip: (n, 2) (ray, sample) whose culling decision is inverted (what a wrong lookup would do to them)
+    acc_dtype: the dtype in which the gradients of the chunks are added up (default float64; a float32 run that is to be a PLAIN fp32 implementation
+    down to its sum over the rays passes float32: one rounding per chunk, in chunk order)
+    kink (MLP shading): every hidden unit of the render MLP decides its ReLU at z + kink x (the fp32 rounding bound of z, as relu_margin forms it)
+    instead of at z.  The results at kink = +1 and -1 bracket what an fp32 evaluation may do at units within rounding of their kink, where the
+    parameter gradient jumps: their distance is the width of that ambiguity for the case"""
     smp = sample_rays(field, rays_o, rays_d, jitter)
     R = smp["o"].shape[0]
     cull = None
@@ -343,17 +356,18 @@ def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=Non
     P = {k: v.detach().to(device=device, dtype=dtype, copy=True).requires_grad_(grads and loss is not None) for k, v in field.p32.items()}
     assert not wrong or field.sh, "the wrong variant is the SH basis's"
     names = [n for n in field.names if not (n.startswith("vel_net") and not plan["steps"])]
-    g = {n: torch.zeros(P[n].shape, dtype=torch.float64, device=device) for n in names}
+    g = {n: torch.zeros(P[n].shape, dtype=acc_dtype, device=device) for n in names}
     outs = {k: [] for k in MAP_KEYS + ("loss_rays",) + (("margin",) if want_margin else ()) + (("margin_ray", "dead") if want_margin and field.sh else ())}
     for s in range(0, len(rays), chunk):
         sl = rays[s:s + chunk]
         with torch.set_grad_enabled(grads and loss is not None):
-            res, terms = _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb, cut_sigma, want_margin, cut_warp, wrong)
+            res, terms = _chunk(field, P, smp, sl, plan, white_bg, app_mask, loss, R, dtype, device, cut_rgb, cut_sigma, want_margin, cut_warp, wrong,
+                                kink)
             if terms is not None and grads:
                 gi = torch.autograd.grad(terms.sum(), [P[n] for n in names], allow_unused=True)
                 for n, x in zip(names, gi):
                     if x is not None:
-                        g[n] += x.to(torch.float64)
+                        g[n] += x.to(acc_dtype)
         for k in outs:
             if k == "loss_rays":
                 outs[k].append(np.zeros(len(sl)) if terms is None else terms.detach().to(torch.float64).cpu().numpy())
@@ -364,7 +378,7 @@ def render64(field, rays_o, rays_d, t, jitter, white_bg, app_mask=None, loss=Non
     if cull is not None:
         out.update(cull)
     out["loss"] = float(out["loss_rays"].sum())
-    out["grads"] = {n: (g[n].cpu().numpy() if n in g else None) for n in field.names} if (grads and loss is not None) else None
+    out["grads"] = {n: (g[n].to(torch.float64).cpu().numpy() if n in g else None) for n in field.names} if (grads and loss is not None) else None
     diff = out["app_mask"] != out["own_mask"]
     out["flips"] = np.argwhere(diff)
     out["flip_dist"] = np.abs(out["weight"][diff].astype(np.float64) - field.thres)
