@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["engine.hip", "wgrad_ring.hip", "vel.hip", "render.hip", "render_rays.hip", "render_app.hip", "render_blocks.hip", "scatter.hip", "scatter_atomic.hip", "mask.hip", "pde.hip", "pde_jet.hip", "pre16.hip", "vel_split.hip", "vel_fuse.hip", "pde_fuse.hip", "regs.hip", "optim.hip", "abi.hip", "comm.hip", "frags.hip", "vel_x6.hip", "vel_x6w.hip", "pde_jet6.hip", "segloss.hip", "metrics.hip", "flow.hip", "objects.hip", "charloss.hip", "depthloss.hip", "advect.hip", "advect_pt.hip", "raydist.hip", "flowloss.hip", "lookup.hip", "point_shade.hip", "maskloss.hip"]
+SOURCES = ["engine.hip", "wgrad_ring.hip", "vel.hip", "render.hip", "render_rays.hip", "render_app.hip", "render_blocks.hip", "scatter.hip", "scatter_atomic.hip", "mask.hip", "pde.hip", "pde_jet.hip", "pre16.hip", "vel_split.hip", "vel_fuse.hip", "pde_fuse.hip", "regs.hip", "optim.hip", "abi.hip", "comm.hip", "frags.hip", "warp.hip", "vel_x6.hip", "vel_x6w.hip", "pde_jet6.hip", "segloss.hip", "metrics.hip", "flow.hip", "objects.hip", "charloss.hip", "depthloss.hip", "advect.hip", "advect_pt.hip", "raydist.hip", "flowloss.hip", "lookup.hip", "point_shade.hip", "maskloss.hip"]
 # every header under csrc/ (engine16.h, ... - a header that is not listed here would leave stale objects behind) + the public ABI
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("nvfi_hip.h", "nvfi_hip_advect_pt.h")]
 SO = os.environ.get("NVFI_BUILD_SO", os.path.join(CSRC, "libnvfi_hip.so"))   # experiments build a second library elsewhere

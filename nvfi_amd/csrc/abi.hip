@@ -6,9 +6,8 @@
 #include "common.h"
 #include "pde.h"
 #include "render.h"
-#include "vel.h"
 #include "x6.h"
-#include "frags.h"
+#include "warp.h"
 
 static thread_local char g_err[512] = "";
 int nvfi_fail(int code, const char* fmt, ...) {
@@ -56,17 +55,10 @@ extern "C" int nvfi_vel_workspace_bytes(const nvfi_field_desc* f, int64_t N, int
     *bytes = align_up((int64_t)2 * VEL_FRAG_FLOATS * 4 + 4096 + N * 16 + N * 12, 256);
     return 0;
 }
-// what both point queries of the velocity net refuse before anything is launched: a descriptor the kernels are not built for, and a field
-// without a velocity net (vW / vb / aW / ab are NULL there: the pack kernels would read through them)
-static int check_vel_call(const nvfi_field_desc* f, const char* call) {
-    if (check_desc(f)) return 2;
-    if (!f->use_vel) return nvfi_fail(2, "%s needs a field with a velocity net (use_vel = 0)", call);
-    return 0;
-}
 extern "C" int nvfi_vel_eval(const nvfi_field_desc* f, int64_t N, const float* xt, float* u6, int gated,
                              void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (check_vel_call(f, "nvfi_vel_eval")) return 2;
+    if (check_vel_call("nvfi_vel_eval", f, 0, VEL_CALL_DESC)) return 2;      // (N is bounded by the workspace alone)
     if (N <= 0) return 0;
     // the published size (nvfi_vel_workspace_bytes) is the contract, as in nvfi_compute_alpha: anything under it is refused here
     int64_t need = 0; nvfi_vel_workspace_bytes(f, N, &need);
@@ -86,43 +78,31 @@ __global__ void k_pack_xt(int64_t N, const float* x, float4* xw) {
     int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i < N) xw[i] = make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], 0.f);
 }
-// fv: the fp32 fragments (WARP_FP32) or the fp16 images, hi + lo (WARP_FP16IN); x6img: the call's own x6 image (own_x6: WARP_X6 without a fragment cache)
+// fv: the fp32 fragments (WARP_FP32) or the fp16 images, hi + lo (WARP_FP16IN: the fragment region is that warp's img16); x6img: the call's
+// own x6 image (WARP_X6 without a fragment cache)
 struct PosPlan { float* fv; float4* xw; float* x6img; int64_t total; };
 static_assert(VEL_FRAG_FLOATS * 4 >= 2 * PRE16_IMAGE_BYTES, "fragment region holds the fp16 images (hi + lo)");
-static void plan_pos(int64_t N, bool own_x6, void* ws, PosPlan* P) {
+static void plan_pos(const nvfi_field_desc* f, WarpKind kind, int64_t N, void* ws, PosPlan* P) {
     Bump B{(char*)ws, 0, 0};
+    const unsigned own = f->frags ? 0 : warp_need(kind, WARP_POINTS);
     P->fv = B.take<float>(VEL_FRAG_FLOATS);
     P->xw = B.take<float4>(N);
-    P->x6img = own_x6 ? B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
+    P->x6img = (own & VI_X6) ? B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
     P->total = B.off;
 }
 extern "C" int nvfi_integrate_pos(const nvfi_field_desc* f, int64_t N, const float* x, const float* t, const float* base,
                                   float* xk, void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (check_vel_call(f, "nvfi_integrate_pos")) return 2;
+    if (check_vel_call("nvfi_integrate_pos", f, N, VEL_CALL_DESC)) return 2;       // (in front of the empty call's 0)
     if (N <= 0) return 0;
-    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "nvfi_integrate_pos: N too large for one call; chunk the points");
     int64_t need = 0; nvfi_vel_workspace_bytes(f, N, &need);      // the published size covers every PosPlan (static_assert above)
     if (need > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)need);
     const WarpKind kind = warp_kind(f, false, true);
-    PosPlan P; plan_pos(N, kind == WARP_X6 && !f->frags, workspace, &P);
+    PosPlan P; plan_pos(f, kind, N, workspace, &P);
     VelImages VI;
-    if (int rc = vel_images(f, kind == WARP_X6 ? VI_X6 : (kind == WARP_FP32 ? VI_VEL : 0), VelImageRoom{P.fv, nullptr, nullptr, nullptr, nullptr, P.x6img}, &VI, nullptr, 0, st)) return rc;
+    if (int rc = vel_images(f, warp_need(kind, WARP_POINTS), VelImageRoom{P.fv, nullptr, nullptr, nullptr, nullptr, P.x6img}, &VI, nullptr, 0, st)) return rc;
     hipLaunchKernelGGL(k_pack_xt, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, P.xw);
-    if (kind == WARP_X6) {
-        X6Args xa; memset(&xa, 0, sizeof(xa));
-        xa.f = *f; xa.img = VI.x6; xa.n_direct = N; xa.xw = P.xw; xa.xout3 = xk; xa.pt_t = t; xa.pt_base = base; xa.dt_max = dt_max_of(*f); xa.max_steps = 4096;
-        return launch_rk2_x6(xa, N, st);
-    }
-    if (kind == WARP_FP16IN) {      // opt-in fp16-input inference mode (pre16.hip): the fragment region of the workspace holds the fp16 image
-        Rk16Args h; memset(&h, 0, sizeof(h));
-        h.img = P.fv; h.P = N; h.xw = P.xw; h.xout3 = xk; h.pt_t = t; h.pt_base = base; h.dt_max = dt_max_of(*f); h.max_steps = 4096;
-        return launch_rk2_inf16(f, h, false, st);
-    }
-    Rk2Args a; memset(&a, 0, sizeof(a));
-    a.f = *f; a.Wv = VI.VW; a.count = nullptr; a.n_direct = N; a.list = nullptr; a.xw = P.xw; a.xout = xk;
-    a.pt_t = t; a.pt_base = base; a.dt_max = dt_max_of(*f); a.max_steps = 4096;
-    return launch_rk2_fwd(a, N, false, st);
+    return warp_points(f, kind, VI, P.fv, WarpPoints{nullptr, N, nullptr, P.xw, xk, t, base, 0, 4096}, st);
 }
 
 // ---------------------------------------------------------------- compute_alpha / device-side rays (next rows f-3, f-2)
@@ -161,7 +141,7 @@ extern "C" int nvfi_compute_alpha(const nvfi_field_desc* f, int64_t N, const flo
                                   int accumulate_max, float* alpha_out, void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (N <= 0) return 0;
-    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "N too large for one call; chunk the points");
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "N too large for one call; chunk the points");
     AlphaPlan AP; plan_alpha(N, workspace, &AP);
     float* fv = AP.fv; float4* xw = AP.xw; float* sig = AP.sig;
     // the published size (nvfi_alpha_workspace_bytes) is the contract whichever integrator the call takes: refused here, before anything is launched
@@ -182,11 +162,9 @@ extern "C" int nvfi_compute_alpha(const nvfi_field_desc* f, int64_t N, const flo
         float* tt = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + AP.total);
         float* tb = tt + N;
         if (AP.total + 2 * N * (int64_t)sizeof(float) > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld", (long long)(AP.total + 8 * N));
-        if (int rc = vel_images(f, VI_X6, VelImageRoom{nullptr, nullptr, nullptr, nullptr, nullptr, AP.x6img}, &VI, nullptr, 0, st)) return rc;
+        if (int rc = vel_images(f, warp_need(kind, WARP_POINTS), VelImageRoom{nullptr, nullptr, nullptr, nullptr, nullptr, AP.x6img}, &VI, nullptr, 0, st)) return rc;
         hipLaunchKernelGGL(k_alpha_times, dim3(nb), dim3(256), 0, st, N, t, base, tt, tb);
-        X6Args xa; memset(&xa, 0, sizeof(xa));
-        xa.f = *f; xa.img = VI.x6; xa.n_direct = N; xa.xw = xw; xa.pt_t = tt; xa.pt_base = tb; xa.dt_max = dt_max_of(*f); xa.max_steps = 4096;
-        if (launch_rk2_x6(xa, N, st)) return 1;
+        if (warp_points(f, kind, VI, nullptr, WarpPoints{nullptr, N, nullptr, xw, nullptr, tt, tb, 0, 4096}, st)) return 1;
     } else if (n != 0) {
         if (n < 0) return nvfi_fail(2, "t=%g needs more than %d RK2 steps", t, MAX_RK_STEPS);
         if (kind == WARP_FP16IN) {  // opt-in fp16-input inference mode (pre16.hip)

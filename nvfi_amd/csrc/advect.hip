@@ -5,19 +5,18 @@
 // Nothing is kept between the forward (nvfi_integrate_pos, which saves no stash) and this call: the warp is run again here on the uniform
 // schedule from t to t_target in training form, and the render's own adjoint chain follows on that stash:
 //   k_advect_pack                                  (N,3) x / g_xk -> dense float4, the identity list, the device count
-//   launch_rk2_x6_uni / launch_rk2_split_uni       the stash-writing warp of a training render (warp_kind(f, true, false); plain stash, z_x4 = 0)
-//   launch_rk2_split_bwd(gx0)                      k_rk2_split_bwd<true>: the unfused adjoint, which also stores the gradient at the start
+//   warp_uni_fwd (warp.h)                          the stash-writing warp of a training render (advect_kind(f); plain stash, z_x4 = 0)
+//   warp_uni_bwd(gx0)                              k_rk2_split_bwd<true>: the unfused adjoint, which also stores the gradient at the start
 //   launch_vel_wgrad(fused_nslab = 0)              six ring jobs + the slab reduce, ACCUMULATED into grads->vW / vb
 // The adjoint is always the unfused pair, whatever NVFI_RK2_FUSE says: the fused kernel (vel_fuse.hip) has no position output.
 // Everything behind the pack kernel is advect_chain (advect.h), the host-side entry nvfi_flow_loss_bwd (flowloss.hip) and nvfi_advect_grad_pt
-// (advect_pt.hip: per-point times, the same chain on a device-side schedule table) share.
+// (advect_pt.hip: per-point times, the same chain on a device-side schedule table) share.  Which launcher runs, and how its argument block is
+// filled, is warp.hip's: the chain names the schedule and the rooms.
 // All on the caller's stream, no host synchronisation.
 #include <string.h>
 #include "common.h"
-#include "vel.h"
 #include "pde.h"
 #include "render.h"
-#include "frags.h"
 #include "x6.h"
 #include "advect.h"
 
@@ -43,16 +42,16 @@ __global__ __launch_bounds__(256) void k_advect_copy(int64_t n, const float* __r
 // sized like plan_render's `nsteps > 0 && train` block: whole 128-point workgroups of stash tiles, two evaluations per step, the records
 void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKind kind, void* ws, AdvectPlan* P) {
     Bump B{(char*)ws, 0, 0};
-    const bool own = !f->frags;                  // without a fragment cache the images are packed into the call's own room
+    const unsigned own = f->frags ? 0 : warp_need(kind, WARP_ADJOINT);   // without a fragment cache the images are packed into the call's own room
     P->cap_tiles = (N + WG_SAMPLES - 1) / WG_SAMPLES * 4;
     P->count = B.take<int>(16);
     P->list = B.take<int>(N);
     P->xw = B.take<float4>(N + 1);
     P->gxk = B.take<float4>(N);
-    P->vel_frag = own ? B.take<float>(VEL_FRAG_FLOATS) : nullptr;
-    P->vel_x4 = (own && kind == WARP_FP32) ? B.take<float>(VEL_X4F_FLOATS) : nullptr;
-    P->vel_x4b = own ? B.take<float>(VEL_X4B_FLOATS) : nullptr;
-    P->x6img = (own && kind == WARP_X6) ? (void*)B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
+    P->vel_frag = (own & VI_VEL) ? B.take<float>(VEL_FRAG_FLOATS) : nullptr;
+    P->vel_x4 = (own & VI_X4F) ? B.take<float>(VEL_X4F_FLOATS) : nullptr;
+    P->vel_x4b = (own & VI_X4B) ? B.take<float>(VEL_X4B_FLOATS) : nullptr;
+    P->x6img = (own & VI_X6) ? (void*)B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
     P->slabs = B.take<float>((int64_t)ADV_NSLAB * ADV_SLAB_FLOATS * 6);
     const int64_t nev = 2 * (int64_t)nsteps;
     P->zst = B.take<float>(nev * P->cap_tiles * (int64_t)(VEL_Z_REGS * REGF));
@@ -62,16 +61,9 @@ void plan_advect(const nvfi_field_desc* f, int64_t N, int nsteps, WarpKind kind,
     P->total = align_up(B.off, 256);
 }
 
-// the training render's forward kernel family; its opt-in fp16-input forward (vel_fp16 bit 2) is the render's alone: integrate_pos never takes it
-WarpKind advect_kind(const nvfi_field_desc* f) {
-    const WarpKind k = warp_kind(f, true, false);
-    return k == WARP_FP16IN ? (sw(NVFI_RK2_X6) ? WARP_X6 : WARP_FP32) : k;
-}
 static int advect_check(const nvfi_field_desc* f, int64_t N, float t, float t_target, float* dts, float* tcs, int* nsteps) {
     if (N < 0) return nvfi_fail(2, "nvfi_advect_grad: N=%lld", (long long)N);
-    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "nvfi_advect_grad: N too large for one call; chunk the points");
-    if (!f->use_vel) return nvfi_fail(2, "nvfi_advect_grad needs a field with a velocity net (use_vel)");
-    if ((f->vel_fp16 & 3) == 1 || (f->vel_fp16 & 3) == 2) return nvfi_fail(2, "nvfi_advect_grad: the fp16-input modes (vel_fp16 1 / 2) have no adjoint");
+    if (int rc = check_vel_call("nvfi_advect_grad", f, N, VEL_CALL_NO_FP16IN)) return rc;
     *nsteps = rk_schedule_to(*f, t, t_target, dts, tcs);
     if (*nsteps < 0) return nvfi_fail(2, "t=%g -> t_target=%g needs more than %d RK2 steps", t, t_target, MAX_RK_STEPS);
     return 0;
@@ -104,32 +96,17 @@ extern "C" int nvfi_advect_grad(const nvfi_field_desc* f, int64_t N, const float
     if (!workspace || P.total > workspace_bytes) return nvfi_fail(4, "workspace too small: need %lld bytes, got %lld", (long long)P.total, (long long)workspace_bytes);
     hipLaunchKernelGGL(k_advect_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, x, g_xk, P.xw, P.gxk, P.list, P.count);
     LAUNCHCK();
-    return advect_chain(f, P, N, nsteps, dts, tcs, kind, g_x, grads, st);
+    return advect_chain(f, P, N, WarpSchedule{nsteps, dts, tcs, nullptr, nullptr, nullptr}, kind, g_x, grads, st);
 }
 
-// the launches behind the caller's pack kernel (advect.h): shared with nvfi_flow_loss_bwd (flowloss.hip)
-int advect_chain(const nvfi_field_desc* f, const AdvectPlan& P, int64_t N, int nsteps, const float* dts, const float* tcs, WarpKind kind,
-                 float* g_x, const nvfi_grads* grads, hipStream_t st, const float* pt_dt, const float* pt_tc) {
-    const bool pt = pt_dt != nullptr;
+// the launches behind the caller's pack kernel (advect.h): shared with nvfi_flow_loss_bwd (flowloss.hip) and nvfi_advect_grad_pt (advect_pt.hip)
+int advect_chain(const nvfi_field_desc* f, const AdvectPlan& P, int64_t N, const WarpSchedule& s, WarpKind kind, float* g_x,
+                 const nvfi_grads* grads, hipStream_t st) {
     VelImages VI;
-    const unsigned need = VI_VEL | VI_X4B | (kind == WARP_X6 ? VI_X6 : VI_X4F);
-    if (int rc = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, nullptr}, &VI, nullptr, 0, st)) return rc;
-    Rk2Args ra; memset(&ra, 0, sizeof(ra));
-    ra.f = *f; ra.Wv = VI.VW; ra.count = P.count; ra.list = P.list; ra.xw = P.xw; ra.xout = nullptr;
-    ra.nsteps = nsteps; ra.sched = nullptr;
-    if (pt) { ra.pt_t = pt_dt; ra.pt_base = pt_tc; }
-    else for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
-    ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles; ra.z_x4 = 0; ra.gxk = P.gxk;
-    if (kind == WARP_X6) {
-        X6UniArgs xa; xa.r = ra; xa.img = VI.x6;
-        if (pt ? launch_rk2_x6_uni_pt(xa, N, st) : launch_rk2_x6_uni(xa, N, true, st)) return 1;
-    } else {
-        SplitUniArgs ua; ua.r = ra;
-        for (int l = 0; l < 6; ++l) { ua.f4[l] = VI.f4[l]; ua.bv[l] = VI.VW.b[l]; }
-        if (pt ? launch_rk2_split_uni_pt(ua, N, st) : launch_rk2_split_uni(ua, N, true, st)) return 1;
-    }
-    SplitBwdArgs ba; ba.r = ra; ba.gx0 = g_x;
-    for (int l = 0; l < 6; ++l) ba.t4[l] = VI.t4[l];
-    if (pt ? launch_rk2_split_bwd_pt(ba, N, st) : launch_rk2_split_bwd(ba, N, st, true)) return 1;
-    return launch_vel_wgrad(P.zst, P.x0st, P.gst, P.count, (int)P.cap_tiles, 2 * nsteps, BM_SILU, P.slabs, ADV_NSLAB, grads->vW, grads->vb, 1.f, st, 0);
+    if (int rc = vel_images(f, warp_need(kind, WARP_ADJOINT), VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, nullptr}, &VI, nullptr, 0, st)) return rc;
+    Rk2Args ra;
+    warp_uni_args(f, VI, P.count, P.list, P.xw, N, s, WarpStash{P.zst, P.x0st, P.rec, P.gst, P.cap_tiles, 0}, P.gxk, &ra);
+    if (warp_uni_fwd(f, kind, VI, nullptr, ra, true, st)) return 1;
+    if (warp_uni_bwd(VI, ra, g_x, st)) return 1;
+    return launch_vel_wgrad(P.zst, P.x0st, P.gst, P.count, (int)P.cap_tiles, 2 * s.nsteps, BM_SILU, P.slabs, ADV_NSLAB, grads->vW, grads->vb, 1.f, st, 0);
 }

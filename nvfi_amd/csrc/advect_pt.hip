@@ -7,15 +7,11 @@
 //                           step as the identity); its tcur is the time it rests at, so the stash rows of a dead step come from an ordinary,
 //                           finite evaluation.  A point whose schedule does not fit in max_steps (or in MAX_RK_STEPS) takes NO step in this call
 //                           - every step dead, its gradient passes through - and is counted in info[0]: never truncated.
-//   advect_chain(pt table)  k_rk2_x6_uni_pt / k_rk2_split_uni<true, true>, k_rk2_split_bwd<., true>, launch_vel_wgrad over 2 max_steps evaluations
+//   advect_chain(pt table)  warp_uni_fwd / warp_uni_bwd (warp.h) on a WarpSchedule that names the table: k_rk2_x6_uni_pt / k_rk2_split_uni<true, true>,
+//                           k_rk2_split_bwd<., true>; launch_vel_wgrad over 2 max_steps evaluations
 // rk_steps (common.h) stays the one copy of the step loop: both kernels call it.  All on the caller's stream, no host synchronisation.
 #include <string.h>
 #include "common.h"
-#include "vel.h"
-#include "pde.h"
-#include "render.h"
-#include "frags.h"
-#include "x6.h"
 #include "advect.h"
 
 #define ADV_PT_BINS (MAX_RK_STEPS + 2)          // step counts 0 .. 64, then the points beyond
@@ -62,15 +58,13 @@ __global__ __launch_bounds__(256) void k_advect_pt_sched(float dtm, int64_t N, i
     }
 }
 
-static int advect_pt_check(const char* who, const nvfi_field_desc* f, int64_t N) {
+// what: 0 for the step count (every mode has an integrator), VEL_CALL_NO_FP16IN for the adjoint
+static int advect_pt_check(const char* who, const nvfi_field_desc* f, int64_t N, unsigned what) {
     if (N < 0) return nvfi_fail(2, "%s: N=%lld", who, (long long)N);
-    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "%s: N too large for one call; chunk the points", who);
-    if (!f->use_vel) return nvfi_fail(2, "%s needs a field with a velocity net (use_vel)", who);
-    return 0;
+    return check_vel_call(who, f, N, what);
 }
 static int advect_pt_check_grad(const char* who, const nvfi_field_desc* f, int64_t N, int max_steps) {
-    if (int rc = advect_pt_check(who, f, N)) return rc;
-    if ((f->vel_fp16 & 3) == 1 || (f->vel_fp16 & 3) == 2) return nvfi_fail(2, "%s: the fp16-input modes (vel_fp16 1 / 2) have no adjoint", who);
+    if (int rc = advect_pt_check(who, f, N, VEL_CALL_NO_FP16IN)) return rc;
     if (max_steps < 0 || max_steps > MAX_RK_STEPS) return nvfi_fail(2, "%s: max_steps=%d is outside 0 .. %d", who, max_steps, MAX_RK_STEPS);
     return 0;
 }
@@ -84,7 +78,7 @@ static int64_t advect_pt_plan(const nvfi_field_desc* f, int64_t N, int max_steps
 extern "C" int nvfi_advect_pt_steps(const nvfi_field_desc* f, int64_t N, const float* t, const float* t_target, int32_t* steps, int64_t* hist66,
                                     void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = advect_pt_check("nvfi_advect_pt_steps", f, N)) return rc;
+    if (int rc = advect_pt_check("nvfi_advect_pt_steps", f, N, 0)) return rc;
     if (!hist66) return nvfi_fail(2, "nvfi_advect_pt_steps: hist66 is NULL");
     if (N > 0 && (!t || !t_target)) return nvfi_fail(2, "nvfi_advect_pt_steps: t and t_target must be non-NULL");
     HIPCK(hipMemsetAsync(hist66, 0, ADV_PT_BINS * sizeof(int64_t), st));
@@ -124,5 +118,5 @@ extern "C" int nvfi_advect_grad_pt(const nvfi_field_desc* f, int64_t N, const fl
     hipLaunchKernelGGL(k_advect_pt_sched, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dt_max_of(*f), N, max_steps, x, g_xk, t, t_target, P.xw,
                        P.gxk, P.list, P.count, tdt, ttc, reinterpret_cast<unsigned long long*>(info));
     LAUNCHCK();
-    return advect_chain(f, P, N, max_steps, nullptr, nullptr, kind, g_x, grads, st, tdt, ttc);
+    return advect_chain(f, P, N, WarpSchedule{max_steps, nullptr, nullptr, nullptr, tdt, ttc}, kind, g_x, grads, st);
 }

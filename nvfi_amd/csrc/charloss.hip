@@ -225,7 +225,7 @@ extern "C" int nvfi_char_loss(const nvfi_field_desc* f, int64_t N, const float* 
                               float* points0_out, const nvfi_grads* grads, void* workspace, int64_t workspace_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (N <= 0) return nvfi_fail(2, "nvfi_char_loss needs at least one point");
-    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "N too large for one call; chunk the points");
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "N too large for one call; chunk the points");
     if (!f->use_vel) return nvfi_fail(2, "the characteristic loss needs the velocity field (use_vel = 0)");
     if (f->K < 2 || !(f->tmax > 0.f)) return nvfi_fail(2, "the characteristic loss needs at least two keyframes and tmax > 0");
     if (f->Cd != 24 || f->Ca != 48 || f->app_dim < 1 || f->app_dim > 32)

@@ -80,6 +80,8 @@ void prof_end(int cls, hipStream_t st);
 struct ProfScope { int c; hipStream_t s; ProfScope(int cls, hipStream_t st) : c(cls), s(st) { prof_begin(c, s); } ~ProfScope() { prof_end(c, s); } };
 
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+// points (or ray samples) of one call: the kernels count them in an int, and a grid of 256-thread workgroups rounds the count up
+static const int64_t POINTS_PER_CALL_MAX = (1ll << 31) - 256;
 
 // simple bump allocator over the caller's workspace
 struct Bump {

@@ -6,16 +6,14 @@
 //   k_flow_gather    x_j (the UN-warped normalised sample position, the fp32 arithmetic of k_sample_fill) and t for every masked sample,
 //                    into the compacted arrays xt (the velocity net's input) and xd (the integrator's in-place state), + the per-point times
 //   launch_vel_eval  v_g(x_j, t): the gated VelBasis evaluation behind nvfi_vel_eval, sized by the device-side count
-//   launch_rk2_x6    Phi(x_j) = integrate_pos(x_j, t, t + dt): the per-point integrator behind nvfi_integrate_pos (x6; vel_fp16 bit 3 or
-//   / launch_rk2_fwd NVFI_INTEGRATE_X6=0: the fp32 MFMA kernel), in place on xd, sized by the device-side count
+//   warp_points      Phi(x_j) = integrate_pos(x_j, t, t + dt): the per-point integrator behind nvfi_integrate_pos (warp.h: x6; vel_fp16 bit 3 or
+//                    NVFI_INTEGRATE_X6=0: the fp32 MFMA kernel), in place on xd, sized by the device-side count
 //   k_flow_final     per-ray ordered sums through off_m with the world scaling and the pinhole projection in the epilogue
 // No MFMA code is instantiated here (the launchers live in vel.hip / vel_x6.hip / vel_x6w.hip), so the unit needs no packed-fp32 fence.
 #include <string.h>
 #include "common.h"
 #include "render.h"
-#include "vel.h"
-#include "x6.h"
-#include "frags.h"
+#include "warp.h"
 
 struct FlowArgs {
     nvfi_field_desc f;
@@ -114,11 +112,9 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
     hipStream_t st = (hipStream_t)stream;
     if (R <= 0) return 0;
     if (flags & NVFI_TRAIN) return nvfi_fail(2, "nvfi_render_flow is an inference branch: NVFI_TRAIN renders have none");
-    if (!f->use_vel) return nvfi_fail(2, "nvfi_render_flow needs a field with a velocity net (use_vel = 0)");
+    if (check_vel_call("nvfi_render_flow", f, 0, VEL_CALL_NO_FP16IN)) return 2;       // (the descriptor and R * S: render_plan_at and the forward)
     if (!(flags & NVFI_WANT_FLOW)) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
-    const int vf = f->vel_fp16 & 3;
-    if (vf == 1 || vf == 2) return nvfi_fail(2, "nvfi_render_flow has no fp16-input integrator (vel_fp16 = %d): use 0, 3 or bit 3", f->vel_fp16);
-    RenderPlan P;      // the forward's: the masked list, its per-ray offsets, the device-side counts, and the flow branch's own room
+    RenderPlan P;     // the forward's: the masked list, its per-ray offsets, the device-side counts, and the flow branch's own room
     const int rc = render_plan_at(f, R, flags, t, workspace, workspace_bytes, &P);
     if (rc == 4)
         return nvfi_fail(2, "workspace of %lld bytes, a plan with NVFI_WANT_FLOW needs %lld: nvfi_render_flow needs a workspace planned with the flag", (long long)workspace_bytes, (long long)P.total);
@@ -127,18 +123,10 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
     if (!P.flow_xt) return nvfi_fail(2, "nvfi_render_flow needs a workspace planned with NVFI_WANT_FLOW in flags");
     const bool want2d = flow2d && pose3x4, want_flow = flow_map || want2d;
     if (!vel_map && !want_flow) return 0;
-    // the integrator's own recurrence (rk2_point_dt) on the host: a dt that needs more steps than the library's limit is refused, not truncated
-    const float t1 = t + dt, dtm = dt_max_of(*f);
-    {
-        float off = t - t1;
-        int n = 0;
-        while (fabsf(off) > 0.f) {
-            if (n >= MAX_RK_STEPS) return nvfi_fail(2, "dt=%g needs more than %d RK2 steps", dt, MAX_RK_STEPS);
-            const float m = fabsf(off) < dtm ? fabsf(off) : dtm;
-            off = off - (off > 0.f ? m : -m);
-            ++n;
-        }
-    }
+    // the integrator's own recurrence on the host (rk_steps): a dt that needs more steps than the library's limit is refused, not truncated
+    const float t1 = t + dt;
+    float dts[MAX_RK_STEPS], tcs[MAX_RK_STEPS];
+    if (rk_schedule_to(*f, t, t1, dts, tcs) < 0) return nvfi_fail(2, "dt=%g needs more than %d RK2 steps", dt, MAX_RK_STEPS);
     const int64_t N = P.N;
     FlowArgs a; memset(&a, 0, sizeof(a));
     a.f = *f; a.R = R; a.cap = N; a.count = count_m; a.inside = P.counters + 2; a.off_m = P.off_m; a.list = P.mlist;
@@ -149,8 +137,9 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
     hipLaunchKernelGGL(k_flow_gather, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
     LAUNCHCK();
     // (vf is 0 or 3 here: WARP_X6 or WARP_FP32)
-    const bool x6 = warp_kind(f, false, true) == WARP_X6, warp = want_flow && t1 != t;
-    const unsigned need = ((vel_map || (want_flow && !x6)) ? VI_VEL : 0) | ((warp && x6) ? VI_X6 : 0);
+    const WarpKind kind = warp_kind(f, false, true);
+    const bool warp = want_flow && t1 != t;
+    const unsigned need = (vel_map ? VI_VEL : 0) | (warp ? warp_need(kind, WARP_POINTS) : 0);
     VelImages VI;
     if (int rc2 = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, nullptr, nullptr, nullptr, P.flow_x6}, &VI, nullptr, 0, st)) return rc2;
     if (vel_map) {
@@ -159,17 +148,7 @@ extern "C" int nvfi_render_flow(const nvfi_field_desc* f, int64_t R, const float
         va.u6 = reinterpret_cast<float*>(P.flow_vg); va.u_stride = 4; va.gated = 1;
         if (launch_vel_eval(va, st)) return 1;
     }
-    if (warp) {
-        if (x6) {
-            X6Args xa; memset(&xa, 0, sizeof(xa));
-            xa.f = *f; xa.img = VI.x6; xa.count = count_m; xa.xw = P.flow_xd; xa.pt_t = P.flow_tb; xa.pt_base = P.flow_tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
-            if (launch_rk2_x6(xa, N, st)) return 1;
-        } else {
-            Rk2Args ra; memset(&ra, 0, sizeof(ra));
-            ra.f = *f; ra.Wv = VI.VW; ra.count = count_m; ra.xw = P.flow_xd; ra.pt_t = P.flow_tb; ra.pt_base = P.flow_tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
-            if (launch_rk2_fwd(ra, N, false, st)) return 1;
-        }
-    }
+    if (warp && warp_points(f, kind, VI, nullptr, WarpPoints{count_m, N, nullptr, P.flow_xd, nullptr, P.flow_tb, P.flow_tb + N, 0, MAX_RK_STEPS}, st)) return 1;
     hipLaunchKernelGGL(k_flow_final, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, a);
     LAUNCHCK();
     return 0;

@@ -6,8 +6,7 @@
 // off_m, the device counts, xw.w); everything it writes lives in the call's own workspace:
 //   k_fl_gather       x_j = normalize_coord(o_r + d_r z_j), z_j = the depth the render used (jitter and the t_min rule are in it), one thread per
 //                     masked entry, sized from the device count; + the per-point times of the integrator and the masked count for the backward
-//   launch_rk2_x6     Phi(x_j) = integrate_pos(x_j, t, t + dt), the no-grad per-point integrator of nvfi_integrate_pos / nvfi_render_flow, in place
-//   / launch_rk2_fwd
+//   warp_points       Phi(x_j) = integrate_pos(x_j, t, t + dt), the no-grad per-point integrator of nvfi_integrate_pos / nvfi_render_flow (warp.h), in place
 //   k_fl_ray          one wave per ray, lanes as in k_flow_final: flow2d[r] as an ordered sum, the error against the target, the ray's loss term (fp64)
 //   k_fl_mean         ONE workgroup: the valid count n and the mean in a fixed order (reduce.h's ordered workgroup sum)
 //   k_fl_grad         one thread per masked entry: g_weights (written behind a zero fill, or added to) and g_xd, the gradient at the displaced point
@@ -18,9 +17,7 @@
 #include <string.h>
 #include "reduce.h"
 #include "render.h"
-#include "vel.h"
 #include "x6.h"
-#include "frags.h"
 #include "advect.h"
 
 #define FL_MEAN_THREADS 1024
@@ -51,16 +48,15 @@ struct FlArgs {
 static void plan_flow_loss(const nvfi_field_desc* f, int64_t R, int nsteps, int64_t chunk_cap, void* ws, FlowLossPlan* P, AdvectPlan* A) {
     Bump B{(char*)ws, 0, 0};
     const int64_t cap = R * (int64_t)f->n_samples;
-    const bool own = !f->frags;
-    const bool x6 = warp_kind(f, false, true) == WARP_X6;
+    const unsigned own = f->frags ? 0 : warp_need(warp_kind(f, false, true), WARP_POINTS);      // the forward's integrator; the chunk plan has its own
     P->hdr = B.take<int>(FL_HDR_INTS);
     P->lterm = B.take<double>(R);
     P->err = B.take<float2>(R);
     P->vflag = B.take<int>(R);
     P->xt = B.take<float4>(cap); P->xd = B.take<float4>(cap); P->gxd = B.take<float4>(cap);
     P->tb = B.take<float>(2 * cap);
-    P->vel_frag = (own && !x6) ? B.take<float>(VEL_FRAG_FLOATS) : nullptr;
-    P->x6img = (own && x6) ? (void*)B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
+    P->vel_frag = (own & VI_VEL) ? B.take<float>(VEL_FRAG_FLOATS) : nullptr;
+    P->x6img = (own & VI_X6) ? (void*)B.take<float>(X6_IMAGE_BYTES / 4) : nullptr;
     P->persist = align_up(B.off, 256);
     P->total = P->persist;
     if (nsteps > 0 && chunk_cap > 0) {
@@ -237,10 +233,8 @@ __global__ __launch_bounds__(256) void k_fl_pack(int64_t first, int64_t cap, con
 
 static int flow_loss_check(const char* who, const nvfi_field_desc* f, int64_t R, float t, float dt, float* dts, float* tcs, int* nsteps) {
     if (R <= 0) return nvfi_fail(2, "%s: R=%lld, at least one ray is needed", who, (long long)R);
-    if (!f->use_vel) return nvfi_fail(2, "%s needs a field with a velocity net (use_vel = 0)", who);
-    const int vf = f->vel_fp16 & 3;
-    if (vf == 1 || vf == 2) return nvfi_fail(2, "%s: the fp16-input modes (vel_fp16 = %d) have neither integrator nor adjoint here: use 0, 3 or bit 3", who, f->vel_fp16);
-    if (f->n_samples < 1 || R * (int64_t)f->n_samples >= (1ll << 31) - 256) return nvfi_fail(2, "%s: R * n_samples = %lld is more than one call holds", who, (long long)(R * (int64_t)f->n_samples));
+    if (int rc = check_vel_call(who, f, 0, VEL_CALL_NO_FP16IN)) return rc;
+    if (f->n_samples < 1 || R * (int64_t)f->n_samples >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "%s: R * n_samples = %lld is more than one call holds", who, (long long)(R * (int64_t)f->n_samples));
     *nsteps = rk_schedule_to(*f, t, t + dt, dts, tcs);
     if (*nsteps < 0) return nvfi_fail(2, "%s: dt=%g needs more than %d RK2 steps", who, dt, MAX_RK_STEPS);
     return 0;
@@ -303,19 +297,10 @@ extern "C" int nvfi_flow_loss_fwd(const nvfi_field_desc* f, int64_t R, const flo
     hipLaunchKernelGGL(k_fl_gather, gN, b256, 0, st, a);
     LAUNCHCK();
     if (nsteps > 0) {
-        const bool x6 = warp_kind(f, false, true) == WARP_X6;
+        const WarpKind kind = warp_kind(f, false, true);
         VelImages VI;
-        if (int rc = vel_images(f, x6 ? VI_X6 : VI_VEL, VelImageRoom{P.vel_frag, nullptr, nullptr, nullptr, nullptr, P.x6img}, &VI, nullptr, 0, st)) return rc;
-        const float dtm = dt_max_of(*f);
-        if (x6) {
-            X6Args xa; memset(&xa, 0, sizeof(xa));
-            xa.f = *f; xa.img = VI.x6; xa.count = a.count; xa.xw = P.xd; xa.pt_t = P.tb; xa.pt_base = P.tb + N; xa.dt_max = dtm; xa.max_steps = MAX_RK_STEPS;
-            if (launch_rk2_x6(xa, N, st)) return 1;
-        } else {
-            Rk2Args ra; memset(&ra, 0, sizeof(ra));
-            ra.f = *f; ra.Wv = VI.VW; ra.count = a.count; ra.xw = P.xd; ra.pt_t = P.tb; ra.pt_base = P.tb + N; ra.dt_max = dtm; ra.max_steps = MAX_RK_STEPS;
-            if (launch_rk2_fwd(ra, N, false, st)) return 1;
-        }
+        if (int rc = vel_images(f, warp_need(kind, WARP_POINTS), VelImageRoom{P.vel_frag, nullptr, nullptr, nullptr, nullptr, P.x6img}, &VI, nullptr, 0, st)) return rc;
+        if (warp_points(f, kind, VI, nullptr, WarpPoints{a.count, N, nullptr, P.xd, nullptr, P.tb, P.tb + N, 0, MAX_RK_STEPS}, st)) return 1;
     }
     hipLaunchKernelGGL(k_fl_ray, dim3((unsigned)((R + 3) / 4)), b256, 0, st, a);
     LAUNCHCK();
@@ -344,5 +329,5 @@ extern "C" int nvfi_flow_loss_bwd(const nvfi_field_desc* f, int64_t R, float t, 
     if (nsteps == 0) return 0;                         // Phi is the identity: nothing reaches the net
     hipLaunchKernelGGL(k_fl_pack, dim3((unsigned)((chunk_cap + 255) / 256)), dim3(256), 0, st, first, chunk_cap, P.hdr, P.xt, P.gxd, A.xw, A.gxk, A.list, A.count);
     LAUNCHCK();
-    return advect_chain(f, A, chunk_cap, nsteps, dts, tcs, advect_kind(f), nullptr, grads, st);
+    return advect_chain(f, A, chunk_cap, WarpSchedule{nsteps, dts, tcs, nullptr, nullptr, nullptr}, advect_kind(f), nullptr, grads, st);
 }

@@ -1,5 +1,5 @@
 // frags.h - the packed weight images of a field: the persistent fragment cache (round 5, ABI v5: nvfi_field_desc.frags) and the ONE way a
-// host entry point gets the velocity net's images (vel_images) and learns which warp kernel it is about to launch (warp_kind)
+// host entry point gets the velocity net's images (vel_images).  Which images a warp needs, and which kernel it launches, is warp.h's.
 //
 // The MFMA kernels read the Linear weights in fragment order (engine.h).  Rounds 1-4 repacked them inside every call into the call's
 // workspace - 3 k_pack + 4 k_frag_x4 launches per training iteration for weights that change once per iteration.  nvfi_pack_frags writes
@@ -26,15 +26,5 @@ struct VelImages { VelFrags VW, AW; const float4 *f4[6], *t4[6], *ta4[6]; const 
 int vel_images(const nvfi_field_desc* f, unsigned need, const VelImageRoom& room, VelImages* out, const PackJobs* ride, unsigned have, hipStream_t st);
 // where the render MLP's fragments of a call live: the cache's region, or the call's own room
 float* render_frag_room(const nvfi_field_desc* f, float* own);
-
-// ---------------------------------------------------------------- which kernel warps the samples back to the keyframe
-enum WarpKind { WARP_X6, WARP_FP16IN, WARP_FP32 };
-// per_point: the no-grad integrators with per-point times (nvfi_integrate_pos, nvfi_compute_alpha, nvfi_render_flow); otherwise the render's
-// warp on its uniform step sequence, in training (train) or eval mode.  The table stands beside the definition (frags.hip).
-WarpKind warp_kind(const nvfi_field_desc* f, bool train, bool per_point);
-// the render plan has room for the fp16 images: a WARP_FP16IN render, and an eval render with vel_fp16 = 3, which has always carried it (pinned sizes)
-bool warp_fp16_room(const nvfi_field_desc* f, bool train);
-// the training warp writes the z rows of layers 0..3 as x4 stash blocks (x6 forward + fused adjoint, NVFI_RK2_X4): forward and backward both ask here
-bool warp_stash_x4(const nvfi_field_desc* f);
 
 int launch_pack_all(const PackJobsAll& jobs, const X6PackArgs* x6, hipStream_t st);

@@ -1,5 +1,5 @@
 // frags.hip - every packed weight image of a field: nvfi_frag_cache_bytes / nvfi_pack_frags (all of them in one launch into the field's
-// cache), vel_images (a host entry point's way to the velocity net's images, cached or packed into its own workspace) and warp_kind (frags.h).
+// cache) and vel_images (a host entry point's way to the velocity net's images, cached or packed into its own workspace; frags.h).
 // Reference counterpart: none - the reference's nn.Linear weights are read by ATen as they are (models/velocity_field.py:60-67,
 // models/tensorf_base.py:67-98); this is the MFMA operand layout of those weights.
 #include <string.h>
@@ -129,30 +129,3 @@ int vel_images(const nvfi_field_desc* f, unsigned need, const VelImageRoom& room
     if ((need & ~have & (VI_X6 | VI_X6T)) && launch_pack_x6(f->vW, at.x6, st, (need & VI_X6T) ? at.x6t : nullptr)) return 1;
     return 0;
 }
-
-// ---------------------------------------------------------------- the warp table
-// vf = vel_fp16 & 3 (0: default, 1 / 2: the fp16-input modes of pre16.hip, 3: x6 asked for by name); +4: fp16-input forward of the TRAINING
-// warp; +8: keep the no-grad integrators on the fp32 MFMA kernel.
-//
-//                                          vf = 0                                       vf = 1, 2      vf = 3
-//   per-point, no grad (integrate_pos,     NVFI_INTEGRATE_X6 (default 1) and no +8:     WARP_FP16IN    WARP_X6      +4 has no say
-//   compute_alpha, render_flow)            WARP_X6, otherwise WARP_FP32                 (render_flow refuses these two)
-//   render, eval                           NVFI_RK2_X6 (default 1): WARP_X6,            WARP_FP16IN    WARP_X6      +4 and +8 have no say
-//                                          otherwise WARP_FP32
-//   render, train                          +4: WARP_FP16IN; otherwise NVFI_RK2_X6: WARP_X6, else WARP_FP32 - for every vf; +8 has no say
-//
-// WARP_X6: vel_x6.hip / vel_x6w.hip (fp32 products formed exactly on the 16-bit matrix pipe, tests/test_gpu_x6.py); WARP_FP16IN: pre16.hip; WARP_FP32:
-// vel.hip (per point), vel_split.hip (render).  NVFI_RK2_FUSE / NVFI_RK2_X4 choose the adjoint and stash layout behind the forward (warp_stash_x4), not the forward.
-WarpKind warp_kind(const nvfi_field_desc* f, bool train, bool per_point) {
-    const int vf = f->vel_fp16 & 3;
-    if (train) {
-        if (f->vel_fp16 & 4) return WARP_FP16IN;
-        return sw(NVFI_RK2_X6) ? WARP_X6 : WARP_FP32;
-    }
-    if (vf == 3) return WARP_X6;
-    if (vf != 0) return WARP_FP16IN;
-    const bool x6 = per_point ? (sw(NVFI_INTEGRATE_X6) != 0 && !(f->vel_fp16 & 8)) : sw(NVFI_RK2_X6) != 0;
-    return x6 ? WARP_X6 : WARP_FP32;
-}
-bool warp_fp16_room(const nvfi_field_desc* f, bool train) { return warp_kind(f, train, false) == WARP_FP16IN || (!train && (f->vel_fp16 & 3) == 3); }
-bool warp_stash_x4(const nvfi_field_desc* f) { return warp_kind(f, true, false) == WARP_X6 && sw(NVFI_RK2_X4) && sw(NVFI_RK2_FUSE); }

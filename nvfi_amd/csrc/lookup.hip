@@ -196,11 +196,10 @@ __global__ __launch_bounds__(256) void k_lookup_app_bwd(LookArgs a) {
 }
 
 // ---------------------------------------------------------------- host
-static const int64_t LOOKUP_N_MAX = (1ll << 31) - 256;       // nvfi_density_at's limit
 static int lookup_check(const char* name, const nvfi_field_desc* f, int64_t N, const float* xyzt, const void* other) {
     if (check_desc(f)) return 2;
     if (N <= 0) return -1;
-    if (N >= LOOKUP_N_MAX) return nvfi_fail(2, "%s: N too large for one call; chunk the points", name);
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "%s: N too large for one call; chunk the points", name);
     if (!xyzt || !other) return nvfi_fail(2, "%s: a NULL input", name);
     return 0;
 }

@@ -429,7 +429,7 @@ extern "C" int nvfi_maskfield_fwd(const nvfi_mask_desc* m, int64_t N, const floa
     hipStream_t st = (hipStream_t)stream;
     if (mask_check(m)) return 2;
     if (N <= 0) return 0;
-    if (N >= (1ll << 31) - 256) return nvfi_fail(2, "too many points for one call");
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "too many points for one call");
     if (mask_attrs()) return 1;
     MkPlan P;
     plan_mask(N, train, workspace, &P);

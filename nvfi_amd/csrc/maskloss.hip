@@ -318,7 +318,7 @@ static int ml_mask_check(const char* who, const nvfi_mask_desc* m) {
 }
 static int ml_shape_check(const char* who, int64_t R, int S, int64_t chunk_cap) {
     if (R <= 0) return nvfi_fail(2, "%s: R=%lld, at least one ray is needed", who, (long long)R);
-    if (S < 1 || R * (int64_t)S >= (1ll << 31) - 256) return nvfi_fail(2, "%s: R * n_samples = %lld is more than one call holds", who, (long long)(R * (int64_t)S));
+    if (S < 1 || R * (int64_t)S >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "%s: R * n_samples = %lld is more than one call holds", who, (long long)(R * (int64_t)S));
     if (chunk_cap < WG_SAMPLES || chunk_cap % WG_SAMPLES) return nvfi_fail(2, "%s: chunk_cap=%lld must be a positive multiple of %d", who, (long long)chunk_cap, WG_SAMPLES);
     return 0;
 }

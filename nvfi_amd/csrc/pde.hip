@@ -510,7 +510,7 @@ static int pde_adjoint(const PdeCall& c, const PdeModes& m, const PdePlan& L, co
 static int pde_loss_run(const PdeCall& c) {
     const int64_t P = c.P;
     if (P <= 0) return nvfi_fail(2, "P must be positive");
-    if (P >= (1ll << 31) - 256) return nvfi_fail(2, "P too large");
+    if (P >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "P too large");
     if (!c.f->use_vel) return nvfi_fail(2, "PDE loss needs use_vel");
     if (ensure_lds_attrs()) return 1;
     PdePlan L; plan_pde(P, c.workspace, &L);

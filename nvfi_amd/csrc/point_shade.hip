@@ -18,8 +18,6 @@
 
 #define PS_NSLAB 256                             // slab capacity of a weight-gradient job (one per CU), as the render's
 #define PS_SLAB_FLOATS (128 * 128 + 128)
-// k_app_fwd carries the point count as an int (render_blocks.hip: nvfi_render_mlp's limit)
-static const int64_t PS_N_MAX = (1ll << 31) - 256;
 
 struct PshadeArgs {
     nvfi_field_desc f;
@@ -173,7 +171,7 @@ static void plan_pshade(const nvfi_field_desc* f, int64_t N, void* ws, PshadePla
 
 static int pshade_check(const nvfi_field_desc* f, int64_t N) {
     if (check_desc(f)) return 2;
-    if (N >= PS_N_MAX) return nvfi_fail(2, "nvfi_render_mlp_grad: N too large for one call; chunk the points");
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "nvfi_render_mlp_grad: N too large for one call; chunk the points");
     return 0;
 }
 

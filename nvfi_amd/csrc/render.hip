@@ -10,10 +10,11 @@
 #include "render.h"
 #include "fuse.h"
 #include "pde.h"
-#include "frags.h"
+#include "warp.h"
 #include "x6.h"
 
-// The warp's kernel family (warp_kind) and what it means for the training stash (warp_stash_x4) are frags.h's: NVFI_RK2_X6 (default 1): the x6
+// The warp's kernel family (warp_kind), its images, its launches (warp_uni_*) and what the family means for the training stash (warp_stash_x4)
+// are warp.h's; the fused adjoint (launch_rk2_fuse_bwd) is launched here on the same Rk2Args.  NVFI_RK2_X6 (default 1): the x6
 // kernels; NVFI_RK2_FUSE (default 1): the adjoint + hidden-layer weight gradients in one persistent kernel - then the z rows of layers 0..3 have
 // ONE reader and travel as x4 stash blocks (a quarter of the stash instructions on both sides; NVFI_RK2_X4=0: row-major)
 
@@ -220,8 +221,7 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
     RenderFrags RW; VelImages VI;
     if (pack_render_frags(f, render_frag_room(f, P.render_frag), &RW, &jobs)) return 3;
     const WarpKind kind = warp_kind(f, train, false);
-    const unsigned need = nsteps > 0 ? (VI_VEL | (kind == WARP_X6 ? VI_X6 : (kind == WARP_FP32 ? VI_X4F : 0))) : 0;
-    if (int rc = vel_images(f, need, VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, P.x6imgT}, &VI, &jobs, 0, st)) return rc;
+    if (int rc = vel_images(f, nsteps > 0 ? warp_need(kind, WARP_RENDER) : 0,VelImageRoom{P.vel_frag, nullptr, P.vel_x4, P.vel_x4b, nullptr, P.x6img, P.x6imgT}, &VI, &jobs, 0, st)) return rc;
     // sampling; second compact list (nsteps > 0): the valid samples inside the velocity gate (counters[3])
     SampleArgs sa; memset(&sa, 0, sizeof(sa));
     sa.f = *f; sa.R = R; sa.o = rays_o; sa.d = rays_d; sa.u = jitter; sa.train = train; sa.inside = P.counters + 2;
@@ -230,32 +230,10 @@ static int render_fwd_impl(const nvfi_field_desc* f, int64_t R, const float* ray
     if (launch_sample(sa, P.off_v, P.off_r, fl, st)) return 1;
     // velocity warp back to the keyframe
     if (nsteps > 0) {
-        Rk2Args ra; memset(&ra, 0, sizeof(ra));
-        ra.f = *f; ra.Wv = VI.VW; ra.count = P.counters + 3; ra.list = P.rlist; ra.xw = P.xw; ra.xout = nullptr;
-        ra.nsteps = nsteps; ra.sched = sched;
-        for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
-        ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles;
-        // fp32 form: the feature-split layout of vel_split.hip (the one-tile-per-wave k_rk2_fwd<uniform> of vel.hip, NVFI_RK2_SPLIT=0 - same stash, same
-        // numbers bit for bit - was retired in round 6)
-        // round 5: the warp on the x6 evaluation (vel_x6.hip: the hidden layers' fp32 products formed exactly from three bfloat16 terms per operand
-        // on the 16-bit matrix pipe; same stash / records for the fp32 adjoint) unless NVFI_RK2_X6=0 or an fp16-input mode is asked for
-        if (kind == WARP_X6) {
-            ra.z_x4 = (train && warp_stash_x4(f)) ? 1 : 0;
-            X6UniArgs xa; xa.r = ra; xa.img = VI.x6;
-            if (launch_rk2_x6_uni(xa, N, train, st)) return 1;
-        } else if (kind == WARP_FP16IN) {
-            // opt-in fp16-input modes (pre16.hip): eval-mode renders (bits 0-1), and - bit 2 - the FORWARD of a training render's warp, which
-            // writes the same stash as k_rk2_split_uni<STASH> (the adjoint and the weight gradients stay fp32 MFMA)
-            Rk16Args h; memset(&h, 0, sizeof(h));
-            h.img = P.img16; h.P = N; h.count = P.counters + 3; h.list = P.rlist; h.xw = P.xw; h.xout = P.xw; h.nsteps = nsteps; h.sched = sched;
-            h.zst = P.zst; h.x0st = P.x0st; h.rec = P.rec; h.cap = N; h.cap_tiles = P.cap_tiles;
-            for (int s = 0; s < nsteps; ++s) { h.dt[s] = dts[s]; h.tcur[s] = tcs[s]; }
-            if (launch_rk2_inf16(f, h, true, st, train)) return 1;
-        } else {
-            SplitUniArgs ua; ua.r = ra;
-            for (int l = 0; l < 6; ++l) { ua.f4[l] = VI.f4[l]; ua.bv[l] = VI.VW.b[l]; }
-            if (launch_rk2_split_uni(ua, N, train, st)) return 1;
-        }
+        Rk2Args ra;
+        warp_uni_args(f, VI, P.counters + 3, P.rlist, P.xw, N, WarpSchedule{nsteps, dts, tcs, sched, nullptr, nullptr},
+                      WarpStash{P.zst, P.x0st, P.rec, P.gst, P.cap_tiles, (train && warp_stash_x4(f)) ? 1 : 0}, nullptr, &ra);
+        if (warp_uni_fwd(f, kind, VI, P.img16, ra, train, st)) return 1;
     }
     // density
     DensityArgs da; memset(&da, 0, sizeof(da));
@@ -492,14 +470,11 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
     if (det_mode() && launch_det_finish(f, P.shadow, grads, st)) return 1;
     // RK2 adjoint + velocity-net weight gradients
     if (nsteps > 0) {
-        Rk2Args ra; memset(&ra, 0, sizeof(ra));
-        ra.f = *f; ra.Wv = VI.VW; ra.count = P.counters + 3; ra.list = P.rlist; ra.xw = P.xw;
-        ra.nsteps = nsteps; ra.sched = sched;
-        for (int s = 0; s < nsteps; ++s) { ra.dt[s] = dts[s]; ra.tcur[s] = tcs[s]; }
-        ra.zst = P.zst; ra.x0st = P.x0st; ra.rec = P.rec; ra.gst = P.gst; ra.cap = N; ra.cap_tiles = P.cap_tiles; ra.gxk = P.gxk;
+        Rk2Args ra;
+        warp_uni_args(f, VI, P.counters + 3, P.rlist, P.xw, N, WarpSchedule{nsteps, dts, tcs, sched, nullptr, nullptr},
+                      WarpStash{P.zst, P.x0st, P.rec, P.gst, P.cap_tiles, warp_stash_x4(f) ? 1 : 0 /* what the forward wrote */}, P.gxk, &ra);
         // NVFI_RK2_FUSE (default 1): vel_fuse.hip - the adjoint AND the four 128 x 128 weight gradients in one persistent kernel (no g_1..g_4
-        // stash, no second pass over the z stash); 0: k_rk2_split_bwd + k_wgrad_ring8 over the full adjoint stash
-        ra.z_x4 = warp_stash_x4(f) ? 1 : 0;                              // (what the forward wrote)
+        // stash, no second pass over the z stash); 0: k_rk2_split_bwd + k_wgrad_ring8 over the full adjoint stash (warp_uni_bwd)
         float* vslabs = (fork2 || merge_wgrad) ? P.slabs2 : P.slabs;      // (merged launches: the render MLP's slabs in P.slabs are still live)
         int fused_nslab = 0;
         if (fuse) {
@@ -508,11 +483,7 @@ extern "C" int nvfi_render_bwd_t(const nvfi_field_desc* f, int64_t R, const floa
             for (int l = 0; l < 6; ++l) fa.t4[l] = VI.t4[l];
             fa.imgT = VI.x6t;
             if (launch_rk2_fuse_bwd(fa, N, NSLAB, &fused_nslab, st)) return 1;
-        } else {              // vel_split.hip (k_rk2_bwd of vel.hip, NVFI_RK2_SPLIT_BWD=0 - the same adjoint stash bit for bit - was retired in round 6)
-            SplitBwdArgs ba; ba.r = ra;
-            for (int l = 0; l < 6; ++l) ba.t4[l] = VI.t4[l];
-            if (launch_rk2_split_bwd(ba, N, st)) return 1;
-        }
+        } else if (warp_uni_bwd(VI, ra, nullptr, st)) return 1;
         if (launch_vel_wgrad(P.zst, P.x0st, P.gst, P.counters + 3, (int)P.cap_tiles, 2 * nsteps, BM_SILU, vslabs, NSLAB,
                              grads->vW, grads->vb, 1.f, st, fused_nslab, merge_wgrad ? &mlp_wj : nullptr, merge_wgrad ? &mlp_rj : nullptr)) return 1;
     }

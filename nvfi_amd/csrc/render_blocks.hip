@@ -5,13 +5,12 @@
 
 // ================================================================ building blocks
 // the kernels below carry the point count as an int (k_density_q, k_app_fwd; a larger one would turn negative and the call would write nothing):
-// nvfi_compute_alpha's limit
-static const int64_t POINT_N_MAX = (1ll << 31) - 256;
+// POINTS_PER_CALL_MAX (common.h)
 extern "C" int nvfi_density_at(const nvfi_field_desc* f, int64_t N, const float* xyzt, float* feat, float* sigma, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (check_desc(f)) return 2;
     if (N <= 0) return 0;
-    if (N >= POINT_N_MAX) return nvfi_fail(2, "nvfi_density_at: N too large for one call; chunk the points");
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "nvfi_density_at: N too large for one call; chunk the points");
     DensityArgs da; memset(&da, 0, sizeof(da));
     da.f = *f; da.count = nullptr; da.n_direct = N; da.list = nullptr; da.xw = reinterpret_cast<const float4*>(xyzt);
     da.per_point_t = 1; da.feat_out = feat; da.sigma_out = sigma; da.xpre = nullptr;
@@ -39,7 +38,7 @@ static int app_points(const nvfi_field_desc* f, int64_t N, const float* xyzt, co
                       void* workspace, int64_t workspace_bytes, hipStream_t st) {
     if (check_desc(f)) return 2;
     if (N <= 0) return 0;
-    if (N >= POINT_N_MAX) return nvfi_fail(2, "%s: N too large for one call; chunk the points", xyz3 ? "nvfi_render_mlp" : "nvfi_app_at");
+    if (N >= POINTS_PER_CALL_MAX) return nvfi_fail(2, "%s: N too large for one call; chunk the points", xyz3 ? "nvfi_render_mlp" : "nvfi_app_at");
     Bump B{(char*)workspace, 0, 0};
     float* frag = B.take<float>(RENDER_FRAG_FLOATS);
     float4* out4 = B.take<float4>(N);

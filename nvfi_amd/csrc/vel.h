@@ -110,4 +110,5 @@ __device__ __forceinline__ void vel_stage_w5(float* w5f, const float* W5) {
 #endif
 
 int launch_vel_eval(const VelEvalArgs& a, hipStream_t st);
+// host callers: warp.hip (warp_points: the per-point form) and nvfi_compute_alpha's fixed-schedule branch (abi.hip: the only uniform caller)
 int launch_rk2_fwd(const Rk2Args& a, int64_t cap_samples, bool uniform, hipStream_t st);

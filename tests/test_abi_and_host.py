@@ -386,6 +386,29 @@ def test_reduction_and_point_wave_idioms_have_one_home():
         assert "pointwave.h" in found and found <= homes, f"{what}: {sorted(found)}"
 
 
+def test_warp_dispatch_has_one_home():
+    """The host side of the velocity warp is warp.hip's (text only, comments stripped): the argument blocks of the single warp kernels are named
+    in their defining units, in warp.hip and - X6Args, the PDE prefilter - in pde.hip; the fp32 and fp16-input launchers are called from
+    warp.hip and, once each, from nvfi_compute_alpha's fixed-schedule branch in abi.hip; warp.hip defines no kernel; the point limit of a call
+    is spelled out once; nvfi_render_flow counts RK2 steps with common.h's rk_steps, not with a loop of its own."""
+    csrc = os.path.join(ROOT, "nvfi_amd", "csrc")
+    code = {fn: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, fn), errors="ignore").read(), flags=re.S)
+            for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h"))}
+    assert "warp.hip" in code and "warp.h" in code
+    blocks = {"X6Args": {"x6.h", "vel_x6.hip", "vel_x6w.hip", "warp.hip", "pde.hip"}, "X6UniArgs": {"x6.h", "vel_x6.hip", "vel_x6w.hip", "warp.hip"},
+              "SplitUniArgs": {"pde.h", "vel_split.hip", "warp.hip"}, "SplitBwdArgs": {"pde.h", "vel_split.hip", "warp.hip"}}
+    for name, homes in blocks.items():
+        found = {fn for fn, txt in code.items() if re.search(r"\b%s\b" % name, txt)}
+        assert "warp.hip" in found and found <= homes, f"{name}: {sorted(found - homes)}"
+    for call, own in (("launch_rk2_fwd(", {"vel.h", "vel.hip"}), ("launch_rk2_inf16(", {"pde.h", "pre16.hip"})):
+        counts = {fn: txt.count(call) for fn, txt in code.items() if call in txt and fn not in own}
+        assert set(counts) == {"warp.hip", "abi.hip"} and counts["abi.hip"] == 1, f"{call}: {counts}"
+    assert "__global__" not in code["warp.hip"] and "__global__" not in code["warp.h"]
+    spelled = {fn: txt.count("(1ll << 31) - 256") for fn, txt in code.items() if "(1ll << 31) - 256" in txt}
+    assert spelled == {"common.h": 1}, spelled
+    assert not re.search(r"\bwhile\b", code["flow.hip"])
+
+
 def _plan_desc():
     """nvfi_field_desc with the sizes of golden field A and no pointers: the workspace plan reads sizes only"""
     from nvfi_amd import _lib
@@ -475,15 +498,64 @@ POINT_BYTES = {
 }
 FRAG_CACHE_BYTES = 3125504
 X4_T0_BYTES = 1 * (64 // 4) * 256 * 4      # the x4 copy of weight_net's transposed input layer: 1 tile x 64 K steps (pde.h: X4_FLOATS(1, 64))
+# bytes of the adjoint chains' workspaces for N / R = 1, 128, 129, 4096, generated by running these queries on the library of the commit before
+# warp.h took over the image rooms of plan_advect / plan_flow_loss (default switches).  "<query>:<own|cached>:<RK2 steps>": own - frags NULL, the
+# call packs the images into its own rooms; cached - a non-NULL frags (the size queries test the pointer only)
+CHAIN_SIZES = (1, 128, 129, 4096)
+CHAIN_BYTES = {
+    "nvfi_advect_grad_workspace_bytes:own:1": (104106240, 104119808, 105496832, 147228160),
+    "nvfi_advect_grad_workspace_bytes:own:2": (105482496, 105505792, 108259072, 191579648),
+    "nvfi_advect_grad_workspace_bytes:cached:1": (102827264, 102840832, 104217856, 145949184),
+    "nvfi_advect_grad_workspace_bytes:cached:2": (104203520, 104226816, 106980096, 190300672),
+    "nvfi_advect_grad_pt_workspace_bytes:own:1": (104106496, 104120832, 105498112, 147260928),
+    "nvfi_advect_grad_pt_workspace_bytes:own:2": (105482752, 105507840, 108261376, 191645184),
+    "nvfi_advect_grad_pt_workspace_bytes:cached:1": (102827520, 102841856, 104219136, 145981952),
+    "nvfi_advect_grad_pt_workspace_bytes:cached:2": (104203776, 104228864, 106982400, 190366208),
+    "nvfi_flow_loss_workspace_bytes:own:1": (104528640, 104963328, 106344704, 161261312),
+    "nvfi_flow_loss_workspace_bytes:own:2": (105904896, 106349312, 109106944, 205612800),
+    "nvfi_flow_loss_workspace_bytes:cached:1": (102831872, 103266560, 104647936, 159564544),
+    "nvfi_flow_loss_workspace_bytes:cached:2": (104208128, 104652544, 107410176, 203916032),
+}
+
+
+def _chain_bytes(d):
+    """the three size queries of the adjoint chains for _plan_desc(): nvfi_advect_grad (t one half / one and a half RK2 steps from t_target),
+    nvfi_advect_grad_pt (max_steps 1 / 2), nvfi_flow_loss (dt likewise, chunk_cap = R)"""
+    import ctypes as C
+    from nvfi_amd import _lib
+    L = _lib.lib()
+    dtm = np.float32(0.5) * np.float32(d.tmax) / np.float32(d.K - 1)
+    got = {}
+    for room, frags in (("own", None), ("cached", 256)):
+        d.frags = frags
+        for steps in (1, 2):
+            span = C.c_float(float((np.float32(steps) - np.float32(0.5)) * dtm))
+            queries = {
+                "nvfi_advect_grad_workspace_bytes": lambda n, nb: L.nvfi_advect_grad_workspace_bytes(C.byref(d), C.c_int64(n), span, C.c_float(0.0), nb),
+                "nvfi_advect_grad_pt_workspace_bytes": lambda n, nb: L.nvfi_advect_grad_pt_workspace_bytes(C.byref(d), C.c_int64(n), C.c_int(steps), nb),
+                "nvfi_flow_loss_workspace_bytes": lambda n, nb: L.nvfi_flow_loss_workspace_bytes(C.byref(d), C.c_int64(n), C.c_float(0.0), span, C.c_int64(n), nb),
+            }
+            for name, query in queries.items():
+                row = []
+                for n in CHAIN_SIZES:
+                    nb = C.c_int64(-1)
+                    assert query(n, C.byref(nb)) == 0, (name, room, steps, n, L.nvfi_last_error())
+                    row.append(nb.value)
+                got[f"{name}:{room}:{steps}"] = tuple(row)
+    d.frags = None
+    return got
 
 
 def test_point_workspace_sizes_are_pinned():
     """The published workspace sizes of the PDE term, nvfi_vel_eval / nvfi_integrate_pos, nvfi_compute_alpha and the characteristic loss, and the
     size of the fragment cache, for golden field A's sizes are literals of the parent library.  One moved on purpose: an uncached PDE call packs
-    weight_net's whole transposed x4 set - T0 travels with it, although no PDE kernel reads it - so its workspace is 16 KB larger at every P."""
+    weight_net's whole transposed x4 set - T0 travels with it, although no PDE kernel reads it - so its workspace is 16 KB larger at every P.
+    The adjoint chains (nvfi_advect_grad, nvfi_advect_grad_pt, nvfi_flow_loss_*), whose image rooms come from warp.h's need table: CHAIN_BYTES,
+    with and without a fragment cache, for one and two RK2 steps."""
     import ctypes as C
     from nvfi_amd import _lib
     d = _plan_desc()
+    assert _chain_bytes(d) == CHAIN_BYTES
     assert X4_T0_BYTES == 16384
     for name, want in POINT_BYTES.items():
         got = []

@@ -196,6 +196,18 @@ def test_shapes(ctx, kind, R, steps):
     if R >= 7:
         assert counts[0] == 1 and y64["n"] == R - 2
     _check(dev, y64, y32, f"{kind}:R={R}:{steps} step(s)")
+    if (R, steps) == (SHAPES[0], 1):
+        # the smallest case once more with descriptor bit 3: nvfi_flow_loss_fwd on the fp32 MFMA integrator (k_rk2_fwd<false>, the kernel
+        # tests/test_gpu_point64.py drives through nvfi_integrate_pos) - the same rays, the same render, the same yardstick, the same bound
+        f = c["f"]
+        old = f.vel_fp16
+        f.vel_fp16 = "fp32"
+        try:
+            dev8 = _device(c, o, d, jit, dt, target, valid)
+        finally:
+            f.vel_fp16 = old
+        assert np.array_equal(dev8["weights"], dev["weights"])       # (bit 3 has no say in a training render)
+        _check(dev8, y64, y32, f"{kind}:R={R}:{steps} step(s):fp32-integrator")
 
 
 @pytest.mark.parametrize("kind", "AB")
